@@ -6,7 +6,7 @@ Darcy residual, PIDM loss) -> zero_grad -> backward -> [gradient all-reduce when
 Adam.step, on synthetic Darcy-shaped fields already resident in HBM, fp32, default torch init under seed 0.
 Workload = BASELINE.json configs[1] (batch 64 per GPU; configs[2] = 8 x 64 under weak scaling).
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -15,7 +15,10 @@ main.py:102-109,126,139); --workload sampling = configs[4] (sample.py:145-150: D
 batch 1024; a step = ONE p_sample step of the whole batch: UNet forward + residual + ancestral update, `value` in
 sample-steps/s).  Same JSON schema, roofline and cpu_baseline for all three.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
+Rank 0 prints ONE JSON line: metric, value, unit, higher_is_better, dtype, ms_per_step (one timed step), steps, warmup, config,
+launches, step_flop_fraction.  A plain run sets up, warms up, times --steps steps and prints it; `--dump-outputs DIR` also writes
+what the last timed step computed (see dump_outputs).  `--full` then measures the secondary figures below (null without it;
+the mechanics_b32 / sampling_b1024 keys are left out):
   roofline     - the dominant kernel class (implicit-GEMM conv fwd/dgrad + wgrad on the matrix cores):
                  algorithmic FLOPs / HIP-event time of those launches, measured live on the launch stream
   fp32_mfma_only - the same step with every contraction on the fp32 MFMA instead of the split-bf16 form
@@ -47,6 +50,7 @@ import time
 # variable must be in place before the HIP runtime starts
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -80,7 +84,47 @@ def parse(argv=None):
                     help="use torch clip_grad_norm_ + torch.optim.Adam instead of the fused flat clip+Adam kernel (same math)")
     ap.add_argument("--calib-copy", action="store_true",
                     help="also run one 1 GiB device copy (known byte count for the PMC traffic passes, tools/pmc_traffic.sh)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps also measure the secondary figures (roofline, fp32_mfma_only, eager_scalars, "
+                         "dropin_main_py, north_star_b256, residual_only, exchange, the mechanics / sampling legs, cpu_baseline); "
+                         "the --no-* options switch single ones off again")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64; a seeded sample of a large "
+                         "array)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_cpu_baseline = args.no_alt = args.no_roofline = True
+    return args
+
+
+DUMP_MAX_ELEMS = 3_000_000      # per array (12 MB of float32): the at most four arrays of a dump stay below 64 MB
+
+
+def _dump_array(path, t, seed):
+    """`t` as float32 DIR/<name>.npy; a tensor of more than DUMP_MAX_ELEMS elements as the same seeded sample (sorted flat indices)
+    in every run, so that two builds can be compared output for output."""
+    t = t.detach()
+    if t.numel() > DUMP_MAX_ELEMS:
+        idx = torch.randint(t.numel(), (DUMP_MAX_ELEMS,), generator=torch.Generator().manual_seed(seed)).sort().values
+        t = t.reshape(-1)[idx.to(t.device)]
+    np.save(path, t.float().cpu().numpy())
+
+
+def dump_outputs(out_dir, model, last, tracked):
+    """What a caller of the timed step holds after its last call (`last` = what the step returned).  Training: the loss, the
+    tracked loss terms (model_estimation_loss's floats), every parameter gradient and the updated parameters (flat,
+    model.parameters() order).  Sampling (tracked None): the chain state p_sample returned."""
+    os.makedirs(out_dir, exist_ok=True)
+    if tracked is None:
+        _dump_array(os.path.join(out_dir, "x.npy"), last, seed=1)
+        return
+    _dump_array(os.path.join(out_dir, "loss.npy"), last, seed=0)
+    np.save(os.path.join(out_dir, "loss_terms.npy"), np.array([float(v) for v in tracked], dtype=np.float64))
+    params = list(model.parameters())
+    _dump_array(os.path.join(out_dir, "grads.npy"), torch.cat([p.grad.reshape(-1) for p in params if p.grad is not None]), seed=2)
+    _dump_array(os.path.join(out_dir, "params.npy"), torch.cat([p.reshape(-1) for p in params]), seed=3)
 
 
 def _oracle_params(m):
@@ -449,6 +493,7 @@ def main(argv=None, test_env=None):
         use_torch = args.torch_optimizer if torch_opt is None else torch_opt
         loss, *tracked = diffusion.model_estimation_loss(b_, residual_func=residuals, **loss_kw)
         counter["it"] += 1
+        counter["tracked"] = tracked
         if counter["it"] % LOG_FREQ == 0:      # main.py:167-175: the tracked loss terms are read every log_freq = 20 iterations
             counter["last"] = [float(v) for v in tracked]
         o_.zero_grad()
@@ -499,11 +544,13 @@ def main(argv=None, test_env=None):
     lc0 = launch_counts()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     t_enqueued = time.perf_counter() - t0          # the host is done enqueuing; the GPU still works through the queue
     fence()
     elapsed = time.perf_counter() - t0
     lc1 = launch_counts()
+    if args.dump_outputs and rank == 0:            # before any --full leg changes the model
+        dump_outputs(args.dump_outputs, model, last, counter["tracked"] if train else None)
     launches = {
         "kernels_enqueued_one_by_one_per_step": round((lc1[0] - lc0[0]) / args.steps, 1),
         "graph_launches_per_step": round((lc1[1] - lc0[1]) / args.steps, 2),
@@ -562,7 +609,7 @@ def main(argv=None, test_env=None):
 
     # gradient exchange: what ran and how long one exchange takes (events on the stream the collectives run on)
     exch = None
-    if exchange is not None:
+    if exchange is not None and args.full:
         exchange.measure = True
         for _ in range(min(args.steps, 5)):
             step()
@@ -762,7 +809,11 @@ def main(argv=None, test_env=None):
 
     cpu = None
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        threads = max(1, min(32, os.cpu_count() or 1))
+        try:        # OMP_NUM_THREADS (its first field: "16" or "16,8") is the CPU quota of the process where it is set
+            threads = int(os.environ.get("OMP_NUM_THREADS", "").split(",")[0])
+        except ValueError:
+            threads = 0
+        threads = max(1, min(32, threads if threads > 0 else (os.cpu_count() or 1)))
         cpu_b, cpu_steps = {"darcy": (64, 2), "mechanics": (2, 1), "sampling": (32, 3)}[wl]
         cpu = cpu_baseline(wl, cpu_b, cpu_steps, threads)
 

@@ -2,13 +2,15 @@
 build injected (bench.py itself has no test hook and imports nothing from tests/), which runs the script's own rank set-up, per-rank
 shards, the three-phase gradient exchange (parallel.GradientExchange over gloo), the barrier + max-over-ranks timing and the JSON
 line at a tiny size.  What is checked is the CONTRACT (n_gpus, exchange, value = global batch x steps / time), not a
-rate.  Also: `--gpus N` must agree with the torch.distributed environment, and without one bench.py launches the ranks itself."""
+rate (the exchange figures are a --full leg).  Also: `--gpus N` must agree with the torch.distributed environment, and without one
+bench.py launches the ranks itself; a plain run times exactly --steps steps, and `--dump-outputs` writes what the last one computed."""
 import json
 import os
 import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -55,7 +57,7 @@ def test_bench_script_has_no_test_hook():
 
 def test_two_ranks_under_torchrun():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), DRIVER, "--gpus", "2", "--steps", "2", "--warmup", "1"]
+           "--master-port", str(_free_port()), DRIVER, "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"]
     r = subprocess.run(cmd, env=_env(), capture_output=True, text=True, timeout=900, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]
     _check_two_rank_line(_json_line(r.stdout))
@@ -63,7 +65,7 @@ def test_two_ranks_under_torchrun():
 
 def test_gpus_flag_spawns_the_ranks_itself():
     """`python bench.py --gpus 2` with no WORLD_SIZE: the script launches one rank per GPU itself instead of silently running one."""
-    cmd = [sys.executable, DRIVER, "--gpus", "2", "--steps", "2", "--warmup", "1"]
+    cmd = [sys.executable, DRIVER, "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"]
     r = subprocess.run(cmd, env=_env(), capture_output=True, text=True, timeout=900, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]
     _check_two_rank_line(_json_line(r.stdout))
@@ -74,3 +76,31 @@ def test_gpus_flag_must_match_world_size():
     r = subprocess.run([sys.executable, DRIVER, "--gpus", "4", "--steps", "1", "--warmup", "0"],
                        env=env, capture_output=True, text=True, timeout=300, cwd=REPO)
     assert r.returncode != 0 and "WORLD_SIZE=1" in (r.stderr + r.stdout)
+
+
+def test_plain_run_and_dump_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps: after 3 warm-up steps (graph capture done) the library's launch counters
+    over the timed region, divided by --steps, give the same counts per step for 3 and for 2 steps (one step more or fewer would
+    not).  --dump-outputs DIR writes what the last timed step computed as float32 / float64 .npy files below 64 MB; two runs with
+    the same arguments write the same arrays, a run with one step fewer other parameters."""
+    lines, dumps = {}, {}
+    for tag, steps in (("a", 3), ("b", 3), ("c", 2)):
+        out = tmp_path / tag
+        r = subprocess.run([sys.executable, DRIVER, "--gpus", "1", "--steps", str(steps), "--warmup", "3", "--dump-outputs", str(out)],
+                           env=_env(), capture_output=True, text=True, timeout=900, cwd=REPO)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = lines[tag] = _json_line(r.stdout)
+        assert d["steps"] == steps and d["warmup"] == 3 and d["n_gpus"] == 1 and d["ms_per_step"] > 0
+        files = sorted(os.listdir(out))
+        assert files == ["grads.npy", "loss.npy", "loss_terms.npy", "params.npy"]
+        assert sum(os.path.getsize(out / f) for f in files) < 64e6
+        arrs = dumps[tag] = {f: np.load(out / f) for f in files}
+        for f, a in arrs.items():
+            assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), f
+        assert arrs["loss_terms.npy"].size == 4 and 0 < arrs["grads.npy"].size <= arrs["params.npy"].size
+    per_step = {t: [d["launches"][k] for k in ("kernels_enqueued_one_by_one_per_step", "graph_launches_per_step",
+                                                "kernels_inside_graphs_per_step")] for t, d in lines.items()}
+    assert sum(per_step["a"]) > 0 and per_step["a"] == per_step["b"] == per_step["c"], per_step
+    for f in dumps["a"]:
+        np.testing.assert_array_equal(dumps["a"][f], dumps["b"][f], err_msg=f)
+    assert not np.array_equal(dumps["a"]["params.npy"], dumps["c"]["params.npy"])

@@ -5,7 +5,7 @@ timeout 900 python -m pytest tests -m gpu -x -q > $o/pytest.log 2>&1; echo "pyte
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $o/smoke.log 2>&1; tail -1 $o/smoke.log
 # ---- two ranks on this one GPU over gloo (debug mode of bench.py): the N > 1 control flow on hardware, and the exchange's negotiation for
 # real - RCCL refuses two ranks on one device, so every rank must come back to torch.distributed together (exchange.collective_note)
-PIDM_BENCH_SHARE_GPU=1 timeout 300 python bench.py --gpus 2 --steps 10 --warmup 4 --no-cpu-baseline --no-alt --no-roofline 2>$o/share_gpu.err | tail -1 > $o/bench_two_ranks_one_gpu.json
+PIDM_BENCH_SHARE_GPU=1 timeout 300 python bench.py --gpus 2 --steps 10 --warmup 4 --no-cpu-baseline --no-alt --no-roofline --full 2>$o/share_gpu.err | tail -1 > $o/bench_two_ranks_one_gpu.json
 python -c "
 import json; d=json.load(open('$o/bench_two_ranks_one_gpu.json')); print('2 ranks / 1 GPU:', d['value'], d['n_gpus'], d['exchange'], d['per_rank'])" 2>&1 | cut -c1-900
 # ---- PMC counters of the split-form 3x3 kernels (three separate --pmc passes each, kernel-trace only) ----
@@ -25,21 +25,21 @@ bash tools/pmc_traffic.sh 32 mechanics > $o/pmc_mech.log 2>&1; cp gpurun_out/pmc
 bash tools/pmc_traffic.sh 1024 sampling > $o/pmc_samp.log 2>&1; cp gpurun_out/pmc_traffic_sampling/traffic.json $o/pmc/pmc_traffic_sampling_b1024.json; rm -rf gpurun_out/pmc_traffic_sampling
 cp $o/pmc/*.json profiles/ 2>/dev/null
 # ---- bench lines ----
-timeout 900 python bench.py --steps 20 --warmup 5 2>$o/bench.err | tail -1 > $o/bench.json
-timeout 600 python bench.py --workload mechanics --steps 10 --warmup 4 2>>$o/bench.err | tail -1 > $o/bench_mechanics.json
-timeout 600 python bench.py --workload sampling --steps 20 --warmup 5 2>>$o/bench.err | tail -1 > $o/bench_sampling.json
+timeout 900 python bench.py --steps 20 --warmup 5 --full 2>$o/bench.err | tail -1 > $o/bench.json
+timeout 600 python bench.py --workload mechanics --steps 10 --warmup 4 --full 2>>$o/bench.err | tail -1 > $o/bench_mechanics.json
+timeout 600 python bench.py --workload sampling --steps 20 --warmup 5 --full 2>>$o/bench.err | tail -1 > $o/bench_sampling.json
 # ---- gradient exchange on one GPU (world size 1: the RCCL path, the side stream and the phase events run for real) ----
 # (default collective on GPUs since round 5: the C-ABI communicator, negotiated and self-checked; PIDM_DP_NATIVE=0: torch.distributed)
-PIDM_BENCH_FORCE_EXCHANGE=1 timeout 600 python bench.py --no-cpu-baseline --no-alt --no-roofline --steps 20 2>>$o/bench.err | tail -1 > $o/force_exchange_darcy.json
-PIDM_BENCH_FORCE_EXCHANGE=1 PIDM_DP_NATIVE=0 timeout 600 python bench.py --no-cpu-baseline --no-alt --no-roofline --steps 20 2>>$o/bench.err | tail -1 > $o/force_exchange_darcy_torch.json
-PIDM_BENCH_FORCE_EXCHANGE=1 timeout 600 python bench.py --workload mechanics --no-cpu-baseline --no-alt --no-roofline --steps 10 --warmup 4 2>>$o/bench.err | tail -1 > $o/force_exchange_mechanics.json
-PIDM_BENCH_FORCE_EXCHANGE=1 PIDM_DP_NATIVE=0 timeout 600 python bench.py --workload mechanics --no-cpu-baseline --no-alt --no-roofline --steps 10 --warmup 4 2>>$o/bench.err | tail -1 > $o/force_exchange_mechanics_torch.json
+PIDM_BENCH_FORCE_EXCHANGE=1 timeout 600 python bench.py --no-cpu-baseline --no-alt --no-roofline --full --steps 20 2>>$o/bench.err | tail -1 > $o/force_exchange_darcy.json
+PIDM_BENCH_FORCE_EXCHANGE=1 PIDM_DP_NATIVE=0 timeout 600 python bench.py --no-cpu-baseline --no-alt --no-roofline --full --steps 20 2>>$o/bench.err | tail -1 > $o/force_exchange_darcy_torch.json
+PIDM_BENCH_FORCE_EXCHANGE=1 timeout 600 python bench.py --workload mechanics --no-cpu-baseline --no-alt --no-roofline --full --steps 10 --warmup 4 2>>$o/bench.err | tail -1 > $o/force_exchange_mechanics.json
+PIDM_BENCH_FORCE_EXCHANGE=1 PIDM_DP_NATIVE=0 timeout 600 python bench.py --workload mechanics --no-cpu-baseline --no-alt --no-roofline --full --steps 10 --warmup 4 2>>$o/bench.err | tail -1 > $o/force_exchange_mechanics_torch.json
 # ---- rocprofv3 kernel statistics (overlap off: a kernel that shares the chip has no duration of its own) ----
 for w in darcy mechanics sampling; do
   st=20; [ $w = mechanics ] && st=6
-  (cd /tmp && PIDM_NO_OVERLAP=1 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $o/prof_$w -o p -- python $R/bench.py --workload $w --steps $st --warmup 5 --no-cpu-baseline --no-alt > $o/prof_$w.log 2>&1)
+  (cd /tmp && PIDM_NO_OVERLAP=1 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $o/prof_$w -o p -- python $R/bench.py --workload $w --steps $st --warmup 5 --no-cpu-baseline --no-alt --full > $o/prof_$w.log 2>&1)
 done
-(cd /tmp && PIDM_NO_OVERLAP=1 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $o/prof_darcy_b256 -o p -- python $R/bench.py --batch 256 --steps 8 --warmup 3 --no-cpu-baseline --no-alt > $o/prof_darcy_b256.log 2>&1)
+(cd /tmp && PIDM_NO_OVERLAP=1 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $o/prof_darcy_b256 -o p -- python $R/bench.py --batch 256 --steps 8 --warmup 3 --no-cpu-baseline --no-alt --full > $o/prof_darcy_b256.log 2>&1)
 find $o -name '*.db' -delete; find $o -name '*agent_info.csv' -delete; find $o -name '*kernel_trace.csv' -delete
 # ---- the step against the per-GPU batch ----
 for b in 16 32 64 128 256 512; do
