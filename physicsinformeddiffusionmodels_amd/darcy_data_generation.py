@@ -1,0 +1,322 @@
+"""Darcy training data: the reference's `src/darcy_data_generation.py` with the solve on the gfx950 engine.
+
+The reference draws a log-permeability field from a Karhunen-Loeve expansion (KLE) of an exponential covariance, assembles the
+dense (P^2+4P+1) x P^2 finite-difference system of -div(K grad p) = f_s with Neumann rows and an integral row, and solves it
+with `scipy.linalg.lstsq` (7.2 s per 64 x 64 sample on one CPU core).  Here the same functions keep their names and signatures,
+and the solve runs in `csrc/k_darcy_gen.hip`: one workgroup per sample, KLE synthesis and matrix-free column-scaled CGLS in
+fp64 ("Darcy data generation").  Host-side pieces are the grid, the eigendecomposition of the covariance (the
+reference's exact full `eigh`, cached) and the CSV writing.  There is no CPU fallback for the solve.
+
+    python -m physicsinformeddiffusionmodels_amd.darcy_data_generation --n-samples 10000 --out ./data/darcy/train
+"""
+from __future__ import annotations
+
+import argparse
+import itertools
+import os
+import time
+
+import numpy as np
+import torch
+
+from ._lib import PidmError, get_lib, ptr, stream_ptr
+
+# reference main() defaults (src/darcy_data_generation.py:166-185)
+DEFAULTS = dict(pixels_per_dim=64, pixels_at_boundary=True, domain_length=1., length_scale=0.1, q=64, reverse_dy=True)
+RTOL = 1e-12          # ||S A^T r|| / ||S A^T b|| at which a sample counts as solved (tests/test_darcy_data_generation.py)
+MAX_ITER = 200000     # P = 64 takes ~40-50k iterations
+
+
+# ---- the reference's host functions (same names, signatures and results) ----------------------------------------------------
+
+def uniform_points_pixelwise(n, domain_length, boundary=False, dim=2):
+    xi = []
+    for _ in range(dim):
+        pixel_size = domain_length / n
+        start, end = (0, domain_length) if boundary else (pixel_size / 2, domain_length - pixel_size / 2)
+        xi.append(np.linspace(start, end, num=n))
+    return np.array(list(itertools.product(*xi)))     # x is the outer index
+
+
+def create_f_s(x, y, w=0.125, r=10.):
+    c1 = np.abs(x - 0.5 * w) <= 0.5 * w
+    c2 = np.abs(x - 1 + 0.5 * w) <= 0.5 * w
+    c3 = np.abs(y - 0.5 * w) <= 0.5 * w
+    c4 = np.abs(y - 1 + 0.5 * w) <= 0.5 * w
+    out = np.zeros_like(x)
+    out[np.logical_and(c1, c3)] = r
+    out[np.logical_and(c2, c4)] = -r
+    return out
+
+
+def complete_covariance_matrix(grid, l):
+    dx = grid[:, None, 0] - grid[None, :, 0]
+    dy = grid[:, None, 1] - grid[None, :, 1]
+    return np.exp(-np.sqrt(dx ** 2 + dy ** 2) / l)
+
+
+def compute_eigenpairs(cov_matrix, q):
+    """First q eigenpairs of the covariance, descending (the full scipy.linalg.eigh, as the reference)."""
+    from scipy.linalg import eigh
+    w, v = eigh(cov_matrix)
+    idx = np.argsort(w)[::-1]
+    return w[idx][:q], v[:, idx][:, :q]
+
+
+def KLE_expansion(eigenvalues, eigenvectors, q, grid_points, seed=None):
+    """G = sum_k sqrt(lambda_k) z_k phi_k with z ~ N(0, 1)^q drawn after np.random.seed(seed) (the reference's norm.rvs draws the
+    same numbers as np.random.standard_normal)."""
+    if seed is not None:
+        np.random.seed(seed)
+    z = np.random.standard_normal(q)
+    G = np.zeros(grid_points)
+    for k in range(q):
+        G += np.sqrt(eigenvalues[k]) * z[k] * eigenvectors[:, k]
+    return G, z
+
+
+def create_boundary_idcs(shape):
+    masks = []
+    for sl in ((0, slice(None)), (-1, slice(None)), (slice(None), 0), (slice(None), -1)):
+        m = np.zeros(shape, dtype=np.bool_)
+        m[sl] = 1
+        masks.append(m.reshape(-1))
+    return tuple(masks)          # xmin, xmax, ymin, ymax
+
+
+def create_int_cond(use_trapezoid, shape, d0):
+    if use_trapezoid:
+        c = np.full(shape, 4.)
+        c[0, :] = c[-1, :] = c[:, 0] = c[:, -1] = 2.
+        c[0, 0] = c[0, -1] = c[-1, 0] = c[-1, -1] = 1.
+        return c * (d0 ** 2 / 4.)
+    return np.ones(shape).reshape(-1, 1) / (shape[0] ** 2)
+
+
+def z_of_seed(seed, q):
+    """The KLE coefficients a seed stands for (KLE_expansion without touching the global numpy state)."""
+    return np.random.RandomState(int(seed)).standard_normal(q)
+
+
+# ---- the engine --------------------------------------------------------------------------------------------------------------
+
+class DarcyProblem:
+    """Grid-dependent, sample-independent data of the reference system: spacings, boundary sign, f_s and integral weights."""
+
+    def __init__(self, P, pixels_at_boundary=True, reverse_dy=True, domain_length=1.):
+        if not 8 <= P <= 64:
+            raise PidmError(f"darcy data generation: pixels_per_dim={P} outside [8, 64] (the solve keeps four fp64 P x P fields "
+                            f"in LDS)")
+        self.P, self.pixels_at_boundary, self.reverse_dy = P, bool(pixels_at_boundary), bool(reverse_dy)
+        self.d0 = domain_length / (P - 1) if pixels_at_boundary else domain_length / P
+        self.d1 = -self.d0 if reverse_dy else self.d0
+        # y-min row: +D1 p with reverse_dy, -D1 p without (y-max the opposite), src/darcy_data_generation.py:147-150
+        self.bc_sign = 1.0 if reverse_dy else -1.0
+        pts = uniform_points_pixelwise(P, domain_length, pixels_at_boundary)
+        self.points = pts
+        self.f_s = create_f_s(pts[:, 0], pts[:, 1]).astype(np.float64)
+        self.int_w = np.ascontiguousarray(create_int_cond(self.pixels_at_boundary, (P, P), self.d0), dtype=np.float64).reshape(-1)
+        self._dev = {}
+
+    def on(self, device):
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = (torch.from_numpy(self.f_s).to(device), torch.from_numpy(self.int_w).to(device))
+        return self._dev[key]
+
+
+def _resolve(device, lib):
+    device = torch.device(device) if device is not None else torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
+    if lib is None:
+        if device.type != "cuda":
+            raise PidmError("darcy data generation needs an MI355X (device cuda): the gfx950 solve has no CPU fallback")
+        lib = get_lib()
+    return device, lib
+
+
+def _basis_file(P, l, q, pixels_at_boundary, domain_length):
+    return f"kle_basis_P{P}_l{l!r}_q{q}_b{int(bool(pixels_at_boundary))}_L{domain_length!r}.npy"
+
+
+def kle_basis(P=64, l=0.1, q=64, pixels_at_boundary=True, cache_dir=None, domain_length=1.):
+    """[q, P*P] float64: row k = sqrt(lambda_k) phi_k, the reference's eigenpairs (full eigh of the P^2 x P^2 covariance,
+    descending).  Cached as .npy under cache_dir, keyed by the arguments.  Degenerate eigenpairs make the rows inside a pair
+    depend on the LAPACK build; their span does not."""
+    if q < 1 or q > P * P:
+        raise PidmError(f"kle_basis: q={q} outside [1, P^2={P * P}]")
+    path = os.path.join(cache_dir, _basis_file(P, l, q, pixels_at_boundary, domain_length)) if cache_dir else None
+    if path and os.path.exists(path):
+        return np.load(path)
+    pts = uniform_points_pixelwise(P, domain_length, pixels_at_boundary)
+    lam, phi = compute_eigenpairs(complete_covariance_matrix(pts, l), q)
+    basis = np.ascontiguousarray((np.sqrt(lam)[None, :] * phi).T)
+    if path:
+        os.makedirs(cache_dir, exist_ok=True)
+        np.save(path, basis)
+    return basis
+
+
+def _check_converged(relres, rtol, labels):
+    bad = [labels[i] for i in np.nonzero(~(relres <= rtol))[0]]
+    if bad:
+        raise PidmError(f"darcy solve did not converge (||S A^T r|| / ||S A^T b|| > {rtol:g}) for sample(s) {bad}: raise max_iter")
+
+
+def _launch(lib, device, prob, *, basis=None, z=None, K_in=None, B, max_iter, rtol):
+    P = prob.P
+    f_s, int_w = prob.on(device)
+    K = torch.empty(B, P * P, dtype=torch.float64, device=device)
+    p = torch.empty(B, P * P, dtype=torch.float64, device=device)
+    res = torch.empty(B, dtype=torch.float64, device=device)
+    iters = torch.empty(B, dtype=torch.int32, device=device)
+    relres = torch.empty(B, dtype=torch.float64, device=device)
+    q = 0 if z is None else z.shape[1]
+    lib.check(lib.pidm_darcy_gen(ptr(basis), ptr(z), q, ptr(K_in), P, prob.d0, prob.d1, prob.bc_sign, ptr(int_w), ptr(f_s),
+                                 int(max_iter), float(rtol), ptr(K), ptr(p), ptr(res), ptr(iters), ptr(relres), B,
+                                 stream_ptr(device)), "pidm_darcy_gen")
+    return K, p, res, iters, relres
+
+
+def generate_darcy_batch(seeds, pixels_per_dim=64, q=64, length_scale=0.1, pixels_at_boundary=True, reverse_dy=True,
+                         domain_length=1., basis=None, max_iter=MAX_ITER, rtol=RTOL, cache_dir=None, device=None, lib=None):
+    """Samples for the given seeds: K = exp(KLE(z(seed))) and the reference's least-squares pressure p.
+    Returns (K [B,P*P], p [B,P*P], res [B], iters [B]) on the device, fp64 (res = mean |row residual| over all P^2+4P+1 rows).
+    `basis` ([q, P*P], see kle_basis) overrides the eigendecomposition."""
+    device, lib = _resolve(device, lib)
+    P = pixels_per_dim
+    prob = DarcyProblem(P, pixels_at_boundary, reverse_dy, domain_length)
+    seeds = [int(s) for s in seeds]
+    if basis is None:
+        basis = kle_basis(P, length_scale, q, pixels_at_boundary, cache_dir, domain_length)
+    basis = np.ascontiguousarray(basis, dtype=np.float64)
+    if basis.ndim != 2 or basis.shape[1] != P * P or not 1 <= basis.shape[0] <= P * P:
+        raise PidmError(f"KLE basis of shape {basis.shape} does not fit q <= P^2 = {P * P} modes of {P} x {P}")
+    q = basis.shape[0]
+    z = torch.from_numpy(np.stack([z_of_seed(s, q) for s in seeds]) if seeds else np.zeros((0, q))).to(device)
+    bt = torch.from_numpy(basis).to(device)
+    K, p, res, iters, relres = _launch(lib, device, prob, basis=bt, z=z.contiguous(), B=len(seeds), max_iter=max_iter, rtol=rtol)
+    if device.type == "cuda":
+        torch.cuda.synchronize(device)
+    _check_converged(relres.cpu().numpy(), rtol, [f"#{i} (seed {s})" for i, s in enumerate(seeds)])
+    return K, p, res, iters
+
+
+def solve_darcy_pressure(K, pixels_at_boundary=True, reverse_dy=True, domain_length=1., max_iter=MAX_ITER, rtol=RTOL, lib=None,
+                         return_iters=False):
+    """The reference's least-squares pressure for given permeability fields K ([B,P,P] or [P,P], fp64 on the device).
+    Returns (p shaped like K, res [B]) - and iters [B] with return_iters."""
+    if not isinstance(K, torch.Tensor):
+        raise PidmError("solve_darcy_pressure: K must be a torch tensor on the device")
+    if lib is None and not K.is_cuda:
+        raise PidmError("solve_darcy_pressure needs tensors on an MI355X: the gfx950 solve has no CPU fallback")
+    lib = lib or get_lib()
+    shape = K.shape
+    if K.dim() == 2:
+        K = K.unsqueeze(0)
+    if K.dim() != 3 or K.shape[1] != K.shape[2]:
+        raise PidmError(f"solve_darcy_pressure: K of shape {tuple(shape)} is not [B,P,P] or [P,P]")
+    B, P = K.shape[0], K.shape[1]
+    prob = DarcyProblem(P, pixels_at_boundary, reverse_dy, domain_length)
+    Kin = K.to(torch.float64).reshape(B, P * P).contiguous()
+    _, p, res, iters, relres = _launch(lib, K.device, prob, K_in=Kin, B=B, max_iter=max_iter, rtol=rtol)
+    if K.is_cuda:
+        torch.cuda.synchronize(K.device)
+    _check_converged(relres.cpu().numpy(), rtol, [f"#{i}" for i in range(B)])
+    p = p.reshape(shape)
+    return (p, res, iters) if return_iters else (p, res)
+
+
+def _unique_seeds(n, seed=None):
+    """n distinct seeds in [0, 2^32) - from `seed` when given, else fresh entropy (unique per run, as the reference's
+    pid * time seeds)."""
+    rng = np.random.default_rng(seed)
+    out, seen = [], set()
+    while len(out) < n:
+        for s in rng.integers(0, 2 ** 32, size=n - len(out), dtype=np.uint64).tolist():
+            if s not in seen:
+                seen.add(s)
+                out.append(s)
+    return out
+
+
+def generate_darcy_dataset(n_samples, out_dir, seed=None, seeds=None, batch=256, pixels_per_dim=64, q=64, length_scale=0.1,
+                           pixels_at_boundary=True, reverse_dy=True, domain_length=1., max_iter=MAX_ITER, rtol=RTOL,
+                           cache_dir=None, device=None, lib=None, verbose=False):
+    """Writes out_dir/{seeds,K_data,p_data,res_data}.csv exactly as the reference main() (no header, no index, one row per
+    sample) plus kle_basis.npy (the scaled basis the seeds were expanded in: a seed fixes K only together with it).
+    `seeds` (explicit, must be distinct) or `seed` (draws n_samples distinct seeds reproducibly); neither: fresh ones."""
+    import pandas as pd
+    if seeds is None:
+        seeds = _unique_seeds(n_samples, seed)
+    seeds = [int(s) for s in seeds]
+    if len(seeds) != n_samples:
+        raise PidmError(f"generate_darcy_dataset: {len(seeds)} seeds for {n_samples} samples")
+    if len(set(seeds)) != len(seeds):
+        dup = sorted({s for s in seeds if seeds.count(s) > 1})
+        raise PidmError(f"Seeds are not unique: {dup}")
+    if batch < 1:
+        raise PidmError("generate_darcy_dataset: batch must be >= 1")
+    P = pixels_per_dim
+    DarcyProblem(P, pixels_at_boundary, reverse_dy, domain_length)     # argument checks before the eigendecomposition
+    basis = kle_basis(P, length_scale, q, pixels_at_boundary, cache_dir, domain_length)
+    Ks, ps, rs = [], [], []
+    t0 = time.time()
+    for lo in range(0, n_samples, batch):
+        K, p, res, iters = generate_darcy_batch(seeds[lo:lo + batch], P, q, length_scale, pixels_at_boundary, reverse_dy,
+                                                domain_length, basis=basis, max_iter=max_iter, rtol=rtol, device=device, lib=lib)
+        Ks.append(K.cpu().numpy())
+        ps.append(p.cpu().numpy())
+        rs.append(res.cpu().numpy())
+        if verbose:
+            it = iters.cpu().numpy()
+            print(f"samples {lo}..{lo + len(it) - 1}: iterations {it.min()}..{it.max()}, {time.time() - t0:.1f} s")
+    os.makedirs(out_dir, exist_ok=True)
+    pd.DataFrame(seeds).to_csv(os.path.join(out_dir, "seeds.csv"), index=False, header=False)
+    pd.DataFrame(np.concatenate(Ks) if Ks else np.zeros((0, P * P))).to_csv(os.path.join(out_dir, "K_data.csv"), index=False, header=False)
+    pd.DataFrame(np.concatenate(ps) if ps else np.zeros((0, P * P))).to_csv(os.path.join(out_dir, "p_data.csv"), index=False, header=False)
+    pd.DataFrame(np.concatenate(rs) if rs else np.zeros(0)).to_csv(os.path.join(out_dir, "res_data.csv"), index=False, header=False)
+    np.save(os.path.join(out_dir, "kle_basis.npy"), basis)
+    return seeds
+
+
+def generate_sample(args):
+    """The reference's per-sample worker: same argument tuple, same (K, p, mean |residual|, seed) result; K from the given
+    eigenpairs on the host, the least-squares solve on the engine."""
+    (i, eigenvalues, eigenvectors, q, pixels_per_dim, shape, acc, d0, d1, f_s, int_cond, xmin_bd, xmax_bd, ymin_bd, ymax_bd,
+     reverse_dy) = args
+    if acc != 2:
+        raise PidmError("the gfx950 solve implements acc=2 (model.yaml:13)")
+    unique_seed = os.getpid() * int(time.time() * 1000) % (2 ** 32)
+    G, _ = KLE_expansion(eigenvalues, eigenvectors, q, pixels_per_dim ** 2, seed=unique_seed)
+    K = np.exp(G.reshape(shape))
+    P = pixels_per_dim
+    pixels_at_boundary = np.shape(int_cond) == tuple(shape)      # create_int_cond: trapezoid weights [P,P], else a mean [P^2,1]
+    p, res = solve_darcy_pressure(torch.from_numpy(K).to(_resolve(None, None)[0]), pixels_at_boundary=pixels_at_boundary,
+                                  reverse_dy=reverse_dy, domain_length=abs(d0) * ((P - 1) if pixels_at_boundary else P))
+    return K.flatten(), p.cpu().numpy().flatten(), float(res.cpu()[0]), unique_seed
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="Darcy training data (reference src/darcy_data_generation.py) on the MI355X")
+    ap.add_argument("--n-samples", type=int, default=10)
+    ap.add_argument("--out", default="./data/darcy/")
+    ap.add_argument("--seed", type=int, default=None, help="draw the sample seeds reproducibly (default: fresh per run)")
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--pixels-per-dim", type=int, default=DEFAULTS["pixels_per_dim"])
+    ap.add_argument("--q", type=int, default=DEFAULTS["q"])
+    ap.add_argument("--length-scale", type=float, default=DEFAULTS["length_scale"])
+    ap.add_argument("--pixels-at-boundary", type=int, default=1)
+    ap.add_argument("--reverse-dy", type=int, default=1)
+    ap.add_argument("--max-iter", type=int, default=MAX_ITER)
+    ap.add_argument("--rtol", type=float, default=RTOL)
+    ap.add_argument("--cache-dir", default=None, help="where the KLE basis is cached (default: not cached)")
+    a = ap.parse_args(argv)
+    t0 = time.time()
+    generate_darcy_dataset(a.n_samples, a.out, seed=a.seed, batch=a.batch, pixels_per_dim=a.pixels_per_dim, q=a.q,
+                           length_scale=a.length_scale, pixels_at_boundary=bool(a.pixels_at_boundary),
+                           reverse_dy=bool(a.reverse_dy), max_iter=a.max_iter, rtol=a.rtol, cache_dir=a.cache_dir, verbose=True)
+    print(f"Data generation finished: {a.n_samples} samples in {time.time() - t0:.1f} s -> {a.out}")
+
+
+if __name__ == "__main__":
+    main()

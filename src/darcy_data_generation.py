@@ -1,4 +1,9 @@
-"""Reference module `src/darcy_data_generation.py` is not part of the accelerated path: the finite-difference stencil engine lives in
-csrc/k_darcy.hip, plotting and data generation are host-side utilities of the reference.  Import it from the
-reference checkout if you need it."""
-raise ImportError(__doc__)
+"""Re-export of physicsinformeddiffusionmodels_amd.darcy_data_generation under the reference's module path
+(src/darcy_data_generation.py); `python -m src.darcy_data_generation` runs its main()."""
+from physicsinformeddiffusionmodels_amd.darcy_data_generation import *  # noqa: F401,F403
+from physicsinformeddiffusionmodels_amd import darcy_data_generation as _m
+
+globals().update({k: v for k, v in vars(_m).items() if not k.startswith('__')})
+
+if __name__ == "__main__":
+    _m.main()
