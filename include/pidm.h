@@ -81,6 +81,49 @@ int pidm_darcy_loss_fwd_bwd_t(const float* x0, const float* x0_pred, const float
  *   analytic stencil rows.  x0: [B,2,P,P] (p, K); max_dr_dp: [B]. */
 int pidm_darcy_jacobian_max(const float* x0, float inv_h0, float inv_h1, float* max_dr_dp, int B, int P, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Classed stencil operators (k_stencil.hip)     replaces StencilGradientComputation src/grad_utils.py:27-146
+ *   (nine depthwise convolutions + nine slice scatters per operator) and StencilGradients.forward :161-175.
+ * An operator is what the reference's constructor builds from a findiff stencil dictionary: `mio` = largest |offset| of the
+ * ('C','C') stencil, `max_offset` = largest over the other eight classes, and a tap list per position class.  Pixel (i, j) of an
+ * H x W image has row class L (0) if i < mio, H (2) if i >= H - mio, else C (1); columns alike with W; its value is the sum, in
+ * table order, of coefficient * x[i + di, j + dj] over the taps of class 3 * row class + column class.  periodic != 0: only class
+ * 4 (C, C), indices wrapped (F.pad(mode='circular'), :76-81).
+ * table (device, int32 words): [2c], [2c+1] = first tap and number of taps of class c (c = 0..8); [18] mio, [19] max_offset,
+ * [20] taps in total, [21..23] reserved; from word 24 on three words per tap: di, dj, fp32 bits of the coefficient.
+ * Up to PIDM_STENCIL_MAX_TAPS taps per class.  mio / max_offset / ntaps of the descriptor are the launcher's copy of words 18-20 (the
+ * launcher never reads device memory); the kernels clamp what they read from the table to them.
+ * Non-periodic needs H, W >= max(2 mio, mio + max_offset), periodic H, W >= 2 mio + 1 (an error otherwise: the reference
+ * differentiates its zero padding there).
+ * ------------------------------------------------------------------------------------------- */
+#define PIDM_STENCIL_MAX_OPS 5
+#define PIDM_STENCIL_MAX_TAPS 49
+typedef struct pidm_stencil_op {
+  const int32_t* table;
+  int mio, max_offset, ntaps;
+} pidm_stencil_op;
+/* K operators (1..5) on N images x[n * x_stride + i * W + j] in ONE launch, one read of x:
+ * outs_host[k][n * out_stride + i * W + j] = (S_k x_n)[i, j].  ops_host and outs_host are HOST arrays read during the call (each
+ * output has its own base pointer, all share the image stride: a [.., K, H, W] stack is written directly).  Strides in floats. */
+int pidm_stencil_apply(const float* x, long long x_stride, const pidm_stencil_op* ops_host, float* const* outs_host, int K,
+                       long long out_stride, int N, int H, int W, int periodic, void* stream);
+/* adjoint: gx[n * gx_stride + ..] = (add ? add[n * add_stride + ..] : 0) + sum_k S_k^T g_k, as a gather in a fixed order (k, then
+ * class, then tap): no atomics, bit-identical run to run.  gs_host: HOST array of the K cotangent base pointers (image stride
+ * g_stride).  Replaces the autograd backward of the convolutions / scatters above. */
+int pidm_stencil_apply_adjoint(const float* const* gs_host, long long g_stride, const pidm_stencil_op* ops_host, int K,
+                               const float* add, long long add_stride, float* gx, long long gx_stride, int N, int H, int W,
+                               int periodic, void* stream);
+/* Darcy residual for ANY stencil set      replaces src/residuals_darcy.py:137-183 with fd_acc / bcs as constructor arguments.
+ * Same tensors as pidm_darcy_residual_fwd / _bwd; ops4_host = the operators d/d0, d/d1, d2/d0^2, d2/d1^2; bc1_sign = +1 when
+ * reverse_d1 (:175-180); the boundary rows keep their meaning under periodic.  A composition that stays on the device: two
+ * stencil launches + one pointwise kernel forward, the same + the pointwise adjoint + two adjoint launches backward.
+ * workspace: >= pidm_darcy_general_ws(B, P) bytes. */
+size_t pidm_darcy_general_ws(int B, int P);
+int pidm_darcy_residual_general_fwd(const float* x0, const float* f_s, const pidm_stencil_op* ops4_host, int periodic, float bc1_sign,
+                                    float* residual, void* workspace, int B, int P, void* stream);
+int pidm_darcy_residual_general_bwd(const float* x0, const float* grad_res, const pidm_stencil_op* ops4_host, int periodic,
+                                    float bc1_sign, float* grad_x0, void* workspace, int B, int P, void* stream);
+
 /* q-sample  x_t = a[t_b] x0 + am1[t_b] eps          replaces src/denoising_utils.py:633-638
  * writes x_t in channels-last [B,P*P,C] (what the UNet consumes) from NCHW x0/eps. */
 int pidm_qsample_nhwc(const float* x0, const float* eps, const float* a_t, const float* am1_t, float* xt_nhwc,

@@ -30,6 +30,11 @@ class ConvDesc(C.Structure):
                 ("ldo", C.c_int)]
 
 
+class StencilOp(C.Structure):
+    """pidm_stencil_op: one classed stencil operator (device table + the three figures the launcher plans with)."""
+    _fields_ = [("table", C.c_void_p), ("mio", C.c_int), ("max_offset", C.c_int), ("ntaps", C.c_int)]
+
+
 class PidmError(RuntimeError):
     pass
 
@@ -63,6 +68,12 @@ class PidmLib:
         self._sig("pidm_darcy_loss_fwd_bwd", [vp, vp, vp, vp, vp, f, f, f, f, vp, vp, vp, vp, i, i, vp])
         self._sig("pidm_darcy_loss_fwd_bwd_t", [vp, vp, vp, vp, vp, vp, f, f, f, f, vp, vp, vp, vp, i, i, vp])
         self._sig("pidm_darcy_jacobian_max", [vp, f, f, vp, i, i, vp])
+        ll, ops = C.c_longlong, C.POINTER(StencilOp)
+        self._sig("pidm_stencil_apply", [vp, ll, ops, C.POINTER(vp), i, ll, i, i, i, i, vp])
+        self._sig("pidm_stencil_apply_adjoint", [C.POINTER(vp), ll, ops, i, vp, ll, vp, ll, i, i, i, i, vp])
+        self._sig("pidm_darcy_general_ws", [i, i], sz)
+        self._sig("pidm_darcy_residual_general_fwd", [vp, vp, ops, i, f, vp, vp, i, i, vp])
+        self._sig("pidm_darcy_residual_general_bwd", [vp, vp, ops, i, f, vp, vp, i, i, vp])
         self._sig("pidm_qsample_nhwc", [vp, vp, vp, vp, vp, i, i, i, vp])
         self._sig("pidm_qsample_nhwc_t", [vp, vp, vp, vp, vp, vp, i, i, i, vp])
         self._sig("pidm_psample_update", [vp, vp, vp, f, f, f, vp, sz, vp])

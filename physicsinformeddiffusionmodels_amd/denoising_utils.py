@@ -630,8 +630,10 @@ class DenoisingDiffusion(nn.Module):
 
     # ---- training loss (src/denoising_utils.py:616-710) ---------------------------------------------------------
     def _darcy_fast_path_ok(self, residual_func, c_ineq, lambda_opt, x):
-        return (isinstance(residual_func, ResidualsDarcy) and not residual_func.residual_grad_guidance and c_ineq <= 0.
-                and lambda_opt <= 0. and x.dtype == torch.float32 and (x.is_cuda or self._lib is not None))
+        # (the fused loss kernel is second-order, non-periodic: other stencil sets take the unfused path below)
+        return (isinstance(residual_func, ResidualsDarcy) and getattr(residual_func, 'specialised', True)
+                and not residual_func.residual_grad_guidance and c_ineq <= 0. and lambda_opt <= 0. and x.dtype == torch.float32
+                and (x.is_cuda or self._lib is not None))
 
     def _mech_fast_path_ok(self, residual_func, x):
         from .residuals_mechanics_K import ResidualsMechanics

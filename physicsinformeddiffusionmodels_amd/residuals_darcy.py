@@ -4,13 +4,17 @@ Same constructor, same attributes (`gov_eqs`, `model`, `f_s`, `trapezoidal_weigh
 `compute_residual(...) -> dict` contract, but the 200 ATen ops of the reference's stencil engine
 (src/grad_utils.py:64-146, called six times from src/residuals_darcy.py:139-145) are ONE hand-written gfx950
 kernel and its adjoint (csrc/k_darcy.hip) reached through the C ABI.  No CPU fallback.
+
+`fd_acc=2, bcs='none'` (the reference's configuration) runs that specialised kernel.  `fd_acc` 4 / 6 and `bcs='periodic'` run the
+general entries on the classed stencil operators of grad_utils (csrc/k_stencil.hip): two stencil launches and one pointwise kernel
+forward, the pointwise adjoint and two adjoint launches backward.
 """
 from __future__ import annotations
 
 import torch
 
 from ._lib import PidmError, get_lib, ptr, stream_ptr
-from .unet_model import generalized_b_xy_c_to_image, generalized_image_to_b_xy_c
+from .grad_utils import GradientsHelper, _ops_array, generalized_b_xy_c_to_image, generalized_image_to_b_xy_c
 
 
 class _DarcyResidualFn(torch.autograd.Function):
@@ -39,19 +43,50 @@ class _DarcyResidualFn(torch.autograd.Function):
         return gx, None, None, None, None
 
 
+class _DarcyResidualGeneralFn(torch.autograd.Function):
+    """The same map for any stencil set (fd_acc 2 / 4 / 6, periodic or not) through pidm_darcy_residual_general_fwd / _bwd."""
+
+    @staticmethod
+    def forward(ctx, x0_pred, f_s, comps, periodic, bc1_sign, lib):
+        x = x0_pred.contiguous().float()
+        B, C, P, _ = x.shape
+        res = torch.empty(B, P * P, 3, dtype=torch.float32, device=x.device)
+        ws = torch.empty(lib.pidm_darcy_general_ws(B, P), dtype=torch.uint8, device=x.device)
+        ops, keep = _ops_array(comps, x.device)
+        lib.check(lib.pidm_darcy_residual_general_fwd(ptr(x), ptr(f_s), ops, int(periodic), bc1_sign, ptr(res), ptr(ws), B, P,
+                                                      stream_ptr(x.device)), "pidm_darcy_residual_general_fwd")
+        ctx.save_for_backward(x)
+        ctx.meta = (comps, periodic, bc1_sign, lib)
+        return res
+
+    @staticmethod
+    def backward(ctx, grad_res):
+        (x,) = ctx.saved_tensors
+        comps, periodic, bc1_sign, lib = ctx.meta
+        B, C, P, _ = x.shape
+        g = grad_res.contiguous().float()
+        gx = torch.empty_like(x)
+        ws = torch.empty(lib.pidm_darcy_general_ws(B, P), dtype=torch.uint8, device=x.device)
+        ops, keep = _ops_array(comps, x.device)
+        lib.check(lib.pidm_darcy_residual_general_bwd(ptr(x), ptr(g), ops, int(periodic), bc1_sign, ptr(gx), ptr(ws), B, P,
+                                                      stream_ptr(x.device)), "pidm_darcy_residual_general_bwd")
+        return gx, None, None, None, None, None
+
+
 class ResidualsDarcy:
     """Drop-in for reference ResidualsDarcy (src/residuals_darcy.py:5-207)."""
 
     def __init__(self, model, fd_acc, pixels_per_dim, pixels_at_boundary, reverse_d1, device='cpu', bcs='none',
                  domain_length=1., residual_grad_guidance=False, use_ddim_x0=False, ddim_steps=0, lib=None):
-        if fd_acc != 2:
-            raise NotImplementedError('the gfx950 stencil kernel implements fd_acc=2 (model.yaml:13)')
-        if bcs == 'periodic':
-            raise NotImplementedError("periodic stencils are not on the accelerated path (reference default bcs='none')")
+        if fd_acc not in (2, 4, 6):
+            raise NotImplementedError(f'fd_acc={fd_acc}: the stencil engine covers accuracy orders 2, 4 and 6')
+        if bcs not in ('none', 'periodic'):
+            raise ValueError(f"bcs={bcs!r}: 'none' or 'periodic'")
         self.gov_eqs = 'darcy'
         self.model = model
         self.pixels_at_boundary = pixels_at_boundary
-        self.periodic = False
+        self.periodic = bcs == 'periodic'
+        self.fd_acc = fd_acc
         self.input_dim = 2
         d0 = domain_length / (pixels_per_dim - 1) if pixels_at_boundary else domain_length / pixels_per_dim
         d1 = -d0 if reverse_d1 else d0
@@ -61,6 +96,9 @@ class ResidualsDarcy:
         self.pixels_per_dim = pixels_per_dim
         self.device = device
         self._lib = lib
+        self.grads = GradientsHelper(d0=d0, d1=d1, fd_acc=fd_acc, periodic=self.periodic, device=device, lib=lib)
+        # fd_acc=2 without periodic wrap is the specialised kernel of k_darcy.hip (and the fused loss of the training step)
+        self.specialised = fd_acc == 2 and not self.periodic
         # stationary source field on pixel centres (src/residuals_darcy.py:41-53,95-104)
         P = pixels_per_dim
         ps = 1.0 / P
@@ -108,7 +146,15 @@ class ResidualsDarcy:
             raise PidmError('ResidualsDarcy needs tensors on an MI355X: the gfx950 kernels have no CPU fallback')
         if self._f_s_flat.device != x0_pred.device:
             self._f_s_flat = self._f_s_flat.to(x0_pred.device)
-        return _DarcyResidualFn.apply(x0_pred, self._f_s_flat, self.inv_h0, self.inv_h1, self.lib)
+        if self.specialised:
+            return _DarcyResidualFn.apply(x0_pred, self._f_s_flat, self.inv_h0, self.inv_h1, self.lib)
+        sg = self.grads.stencil_gradients
+        P = x0_pred.shape[-1]
+        need = max(getattr(sg, m).min_size() for m in ('d_d0', 'd_d1', 'd_d00', 'd_d11'))
+        if x0_pred.shape[-2] != P or P < need:
+            raise ValueError(f'a {x0_pred.shape[-2]} x {P} field does not fit the fd_acc={self.fd_acc} stencils (square, >= {need})')
+        return _DarcyResidualGeneralFn.apply(x0_pred, self._f_s_flat, (sg.d_d0, sg.d_d1, sg.d_d00, sg.d_d11), self.periodic,
+                                             1.0 if self.reverse_d1 else -1.0, self.lib)
 
     def compute_residual(self, input, reduce='none', return_model_out=False, return_optimizer=False,
                          return_inequality=False, sample=False, ddim_func=None, pass_through=False):
@@ -152,7 +198,9 @@ class ResidualsDarcy:
     def jacobian_max(self, x0_img):
         """max over all entries of d residual / d p per sample ([B,2,P,P] -> [B]).  The reference builds the dense
         vmap(jacfwd) Jacobian for this (400 MB per 64x64 sample, src/residuals_darcy.py:217-231); the kernel evaluates the
-        stencil rows analytically."""
+        stencil rows analytically.  Second-order, non-periodic stencils only."""
+        if not self.specialised:
+            raise NotImplementedError("jacobian_max / residual_correction (CoCoGen) implement fd_acc=2, bcs='none' only")
         x = x0_img.detach().contiguous().float()
         B, _, P, _ = x.shape
         out = torch.empty(B, dtype=torch.float32, device=x.device)
@@ -164,6 +212,8 @@ class ResidualsDarcy:
         """CoCoGen correction step (src/residuals_darcy.py:209-238): p <- p - (1e-6 / max dr/dp) * d(sum r^2)/dp,
         applied IN PLACE to x0_pred_in [B, P*P, 2]; returns (x0_pred_in, residual of the corrected field)."""
         assert len(x0_pred_in.shape) == 3, 'Model output must be a tensor shaped as b_xy_c.'
+        if not self.specialised:
+            raise NotImplementedError("jacobian_max / residual_correction (CoCoGen) implement fd_acc=2, bcs='none' only")
         with torch.enable_grad():
             x0_pred = x0_pred_in.detach().clone().requires_grad_(True)
             residual_x0_pred = self.compute_residual(generalized_b_xy_c_to_image(x0_pred), pass_through=True)['residual']

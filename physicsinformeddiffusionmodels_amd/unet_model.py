@@ -44,22 +44,8 @@ def cycle(dl):
             yield data
 
 
-def generalized_image_to_b_xy_c(tensor):
-    """[B, c..., X, Y] -> [B, X*Y, c...]  (reference: src/unet_model.py:12-18)."""
-    nd = tensor.dim()
-    perm = [0, nd - 2, nd - 1] + list(range(1, nd - 2))
-    t = tensor.permute(*perm)
-    return t.reshape(t.shape[0], t.shape[1] * t.shape[2], *t.shape[3:])
-
-
-def generalized_b_xy_c_to_image(tensor, pixels_x=None, pixels_y=None):
-    """[B, X*Y, c...] -> [B, c..., X, Y]  (reference: src/unet_model.py:20-28)."""
-    if pixels_x is None or pixels_y is None:
-        pixels_x = pixels_y = int(math.sqrt(tensor.shape[1]))
-    t = tensor.reshape(tensor.shape[0], pixels_x, pixels_y, *tensor.shape[2:])
-    nd = t.dim()
-    perm = [0] + list(range(3, nd)) + [1, 2]
-    return t.permute(*perm)
+# (the two converters live in grad_utils, where the reference keeps its primary copy; re-exported here: src/unet_model.py:12-28)
+from .grad_utils import generalized_b_xy_c_to_image, generalized_image_to_b_xy_c  # noqa: E402,F401
 
 
 # --------------------------------------------------------------------------------------------------

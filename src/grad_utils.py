@@ -1,4 +1,5 @@
-"""Reference module `src/grad_utils.py` is not part of the accelerated path: the finite-difference stencil engine lives in
-csrc/k_darcy.hip, plotting and data generation are host-side utilities of the reference.  Import it from the
-reference checkout if you need it."""
-raise ImportError(__doc__)
+"""Re-export of physicsinformeddiffusionmodels_amd.grad_utils under the reference's module path (src/grad_utils.py)."""
+from physicsinformeddiffusionmodels_amd.grad_utils import *  # noqa: F401,F403
+from physicsinformeddiffusionmodels_amd import grad_utils as _m
+
+globals().update({k: v for k, v in vars(_m).items() if not k.startswith('__')})
