@@ -224,6 +224,41 @@ int pidm_darcy_gen(const double* basis, const double* z, int q, const double* K_
                    const double* int_w, const double* f_s, int max_iter, double rtol, double* K_out, double* p_out,
                    double* res_mean, int32_t* iters, double* relres, int B, void* stream);
 
+/* Mechanics training-data generation      replaces nothing in the reference: it never generated its topology-optimisation samples
+ * (they were downloaded); these entries supply the data main.py:90-101 expects (one [65,65,10] .npy per sample), DESIGN section 4b
+ *   pidm_simp_step: ONE iteration of SIMP compliance minimisation for B samples, one workgroup per sample, all in fp64, stateless:
+ *                   (x [B, nel*nel] densities, u [B, ndof] warm start) -> (x_new, u_out = the solved displacements).  Per sample:
+ *                     1. E_e = e_min + x_e^penal (1 - e_min)
+ *                     2. K_closed(E) u = f by Jacobi-preconditioned CG on the matrix-free operator of pidm_mech_solve (bcs as there:
+ *                        a non-zero entry of channels 0/1 pins that dof - identity row, f = 0; channels 2/3 are the loads), started
+ *                        from u; stops at ||r|| <= pcg_rtol ||f|| or pcg_max_iter; the initial residual is tested too, so a
+ *                        converged warm start costs 0 iterations and comes back unchanged
+ *                     3. ce_e = u_e^T k_e u_e,  c = sum_e E_e ce_e,  dc_e = -penal x_e^(penal-1) (1 - e_min) max(ce_e, 0)
+ *                        (the fp32 element stiffness is indefinite by its rounding: a rigidly moving element can show ce_e < 0)
+ *                     4. dc~_e = sum_j H_ej x_j dc_j / (max(1e-3, x_e) sum_j H_ej),  H_ej = max(0, rmin - dist(e, j)) over the
+ *                        window of ceil(rmin) - 1 elements each way, clipped at the domain edge
+ *                     5. optimality criteria with exactly n_bisect bisection steps on lambda in [0, 1e9] (no tolerance exit):
+ *                        x_new = max(0, max(x - move, min(1, min(x + move, x sqrt(-dc~ / lambda))))),
+ *                        mean(x_new) > vf => l1 = lambda, else l2 = lambda; the x_new of the last step is the result
+ *                   compliance [B] = c, change [B] = max |x_new - x|, pcg_iters [B], relres [B] = ||r|| / ||f|| at exit.
+ *                   active (int32 [B], may be NULL): a sample with active[b] == 0 is copied through (x_new = x, u_out = u) and its
+ *                   four scalar outputs are not written.  Reductions run in a fixed order: results are bit-identical run to run and
+ *                   across batch sizes.  x_new / u_out must not alias x / u; mesh tables 16-byte aligned.  2 <= nel <= 79 (the search direction and the moduli
+ *                   live in LDS), rmin > 1, n_bisect >= 1, penal >= 1, 0 < e_min < 1.
+ *                   workspace: pidm_simp_ws_bytes(nel, B).
+ *   pidm_mech_fields: nodal conditioning fields of a solved state u_dofs [B, ndof] (fp32, as pidm_mech_solve writes it) with Young's
+ *                   moduli rho [B, nel*nel]: per element, at its centre, the strain energy density 1/2 rho_e u_e^T k_e u_e / area
+ *                   and the plane-stress von Mises stress sqrt(sx^2 - sx sy + sy^2 + 3 txy^2), sigma = rho_e C(nu) B(0,0) u_e, for
+ *                   the regular mesh of unit squares with local nodes (bottom-left, bottom-right, top-right, top-left); every node
+ *                   gets the mean of its 1-4 adjacent elements.  fields [B,2,nel+1,nel+1] (energy density, von Mises), fp32. */
+size_t pidm_simp_ws_bytes(int nel, int B);
+int pidm_simp_step(const double* x, const double* u, const float* bcs, const float* vf, const int32_t* active, const float* kloc,
+                   int kloc_stride, const int32_t* elem_dofs, const int32_t* dof_elems, int nel, double penal, double e_min,
+                   double rmin, double move, int n_bisect, int pcg_max_iter, double pcg_rtol, double* x_new, double* u_out,
+                   double* compliance, double* change, int32_t* pcg_iters, double* relres, void* workspace, int B, void* stream);
+int pidm_mech_fields(const float* u_dofs, const float* rho, const float* kloc, int kloc_stride, const int32_t* elem_dofs, int nel,
+                     double nu, float* fields, int B, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * UNet engine                           replaces Unet3D.forward src/unet_model.py:542-623 + autograd
  * ------------------------------------------------------------------------------------------- */

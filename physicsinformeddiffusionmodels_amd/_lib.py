@@ -84,6 +84,10 @@ class PidmLib:
         self._sig("pidm_darcy_gen_lds_bytes", [i], sz)
         self._sig("pidm_darcy_gen", [vp, vp, i, vp, i, C.c_double, C.c_double, C.c_double, vp, vp, i, C.c_double, vp, vp, vp, vp, vp,
                                      i, vp])
+        d = C.c_double
+        self._sig("pidm_simp_ws_bytes", [i, i], sz)
+        self._sig("pidm_simp_step", [vp, vp, vp, vp, vp, vp, i, vp, vp, i, d, d, d, d, i, i, d, vp, vp, vp, vp, vp, vp, vp, i, vp])
+        self._sig("pidm_mech_fields", [vp, vp, vp, i, vp, i, d, vp, i, vp])
         self._sig("pidm_unet_num_cond_params", [vp])
         self._sig("pidm_unet_enable_cond", [vp, i])
         self._sig("pidm_unet_set_condition", [vp, vp])
