@@ -276,6 +276,12 @@ typedef struct pidm_unet_cfg {
   int image_size;     /* P (square images) */
   int sigmoid_last_channel;
   int self_condition; /* 1: init_conv reads 2*channels inputs, cat(x_self_cond, x) (src/unet_model.py:428,564-566) */
+  int padding_mode;   /* 0: zeros, 1: circular (Unet3D(padding_mode=...), src/unet_model.py:161-199,224-229,424,452-455).  Circular:
+                       * every tap of init_conv, the 3x3 Block.proj, the 4x4/s2 Downsample and the transposed 4x4/s2 upsample that zero
+                       * mode reads as 0 outside the image reads the pixel at the index wrapped modulo the extent - forward, input and
+                       * weight gradients alike; emb_conv.2 of the conditioning branch stays zero-padded (:524).  The upsample
+                       * parameters are then named ups.i.3.conv_transpose.{weight,bias} (CircularUpsample).  Every level needs an
+                       * extent >= 2.  Fixed at pidm_unet_create; a zero-initialised struct gets zero padding. */
 } pidm_unet_cfg;
 
 int pidm_unet_create(const pidm_unet_cfg* cfg, pidm_unet** out);
@@ -327,6 +333,10 @@ typedef struct pidm_conv_desc {
   int transposed;       /* 1: ConvTranspose 4x4 s2 p1 executed as 4 output-parity 2x2 convolutions */
   int out_nchw;         /* 1: write [B,Cout,Ho,Wo] instead of channels-last */
   int ldo;              /* channel stride of the output / residual (channels-last) */
+  int pad_mode;         /* 0: zero padding; 1: circular - a tap outside the input reads the pixel at the index wrapped modulo the
+                         * extent (Hi, Wi powers of two, pad <= extent); honoured by _forward, _forward_gn_partials, _dgrad, _wgrad
+                         * and their workspace / packing queries.  For a transposed convolution the wrap is that of
+                         * out[y] = sum_j x[j mod Hi] w[y + 1 - 2j] (the reference's CircularUpsample). */
 } pidm_conv_desc;
 size_t pidm_conv_packed_weight_floats(const pidm_conv_desc* d);
 /* mode 0: forward pack from [Cout,Cin,KH,KW]; 1: dgrad pack (flipped+transposed) from the same tensor;

@@ -35,6 +35,7 @@ class UnetEngine:
         cfg.image_size = image_size
         cfg.sigmoid_last_channel = int(bool(model.sigmoid_last_channel))
         cfg.self_condition = int(bool(model.self_condition))
+        cfg.padding_mode = {'zeros': 0, 'circular': 1}[getattr(model, 'padding_mode', 'zeros')]
         self.image_size = image_size
         self.handle = vp()
         self.lib.check(self.lib.pidm_unet_create(C.byref(cfg), C.byref(self.handle)), "pidm_unet_create")

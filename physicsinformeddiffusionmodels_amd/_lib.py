@@ -20,14 +20,14 @@ class UnetCfg(C.Structure):
     _fields_ = [("dim", C.c_int), ("channels", C.c_int), ("out_dim", C.c_int), ("n_levels", C.c_int),
                 ("dim_mults", C.c_int * 8), ("heads", C.c_int), ("dim_head", C.c_int), ("groups", C.c_int),
                 ("init_kernel", C.c_int), ("image_size", C.c_int), ("sigmoid_last_channel", C.c_int),
-                ("self_condition", C.c_int)]
+                ("self_condition", C.c_int), ("padding_mode", C.c_int)]   # padding_mode: 0 zeros, 1 circular
 
 
 class ConvDesc(C.Structure):
     _fields_ = [("B", C.c_int), ("Hi", C.c_int), ("Wi", C.c_int), ("C0", C.c_int), ("C1", C.c_int),
                 ("ld0", C.c_int), ("ld1", C.c_int), ("Cout", C.c_int), ("KH", C.c_int), ("KW", C.c_int),
                 ("stride", C.c_int), ("pad", C.c_int), ("transposed", C.c_int), ("out_nchw", C.c_int),
-                ("ldo", C.c_int)]
+                ("ldo", C.c_int), ("pad_mode", C.c_int)]   # pad_mode: 0 zeros, 1 circular
 
 
 class StencilOp(C.Structure):

@@ -1622,9 +1622,12 @@ int launch_conv(const ConvGeom& g, const float* src0, const float* src1, const f
              g.nz, g.gn_part ? " +gnstats" : "", g.bn_part ? " +bnsums" : "", residual ? " +res" : "");
     prof_set_label(lab);
   }
+  // Circular padding (ConvGeom::wrap): the row-streaming 3x3 kernel (k_conv_rs.hip) and the fp32-MFMA kernels of k_conv_fp32.hip
+  // have wrapping variants.  The LDS-staged split-form kernels below stage a zeroed halo and are never selected for a wrapping
+  // convolution.
   if (knob("PIDM_TRACE_CONV"))   // debugging aid: which tile configuration a launch takes
-    fprintf(stderr, "[pidm] conv B=%d %dx%d Cin=%d Cout=%d k=%dx%d nph=%d%s%s%s -> KC=%d NT=%d\n", g.B, g.Hv, g.Wv, g.Cin, g.Cout, g.KH,
-            g.KW, g.nph, g.gn_part ? " +gnstats" : "", g.bn_part ? (g.bn_res ? " +bnsums(res)" : " +bnsums") : "", residual ? " +res" : "", KC,
+    fprintf(stderr, "[pidm] conv B=%d %dx%d Cin=%d Cout=%d k=%dx%d nph=%d%s%s%s%s -> KC=%d NT=%d\n", g.B, g.Hv, g.Wv, g.Cin, g.Cout, g.KH,
+            g.KW, g.nph, g.wrap ? " circular" : "", g.gn_part ? " +gnstats" : "", g.bn_part ? (g.bn_res ? " +bnsums(res)" : " +bnsums") : "", residual ? " +res" : "", KC,
             nt4 ? 4 : NT);
   {
     // 1x1 / stride-1 convolutions as a split-form GEMM (conv1x1_split_kernel): contiguous channels-last input and output, pixel
@@ -1685,7 +1688,7 @@ int launch_conv(const ConvGeom& g, const float* src0, const float* src1, const f
     // the 7x7 init convolution with (kx, channel) flattened into the contraction index, split form (conv7x7_split_kernel)
     const char* se = knob("PIDM_CONV_SPLIT");
     const bool on = !(se && !atoi(se));
-    if (on && g.KH == 7 && g.KW == 7 && g.stride == 1 && g.nz == 1 && g.nph == 1 && g.os == 1 && g.pad_y[0] == 3 && g.pad_x[0] == 3 &&
+    if (on && !g.wrap && g.KH == 7 && g.KW == 7 && g.stride == 1 && g.nz == 1 && g.nph == 1 && g.os == 1 && g.pad_y[0] == 3 && g.pad_x[0] == 3 &&
         g.C1 == 0 && (g.Cin == 2 || g.Cin == 4) && g.ld0 == g.Cin && (g.Cout % 32) == 0 && g.soc == 1 && (g.sox & 3) == 0 &&
         g.Wv == g.Wi && g.Hv == g.Hi && g.Wv >= 8 && g.Wv <= 256 && (256 % g.Wv) == 0 && (g.Hv % (256 / g.Wv)) == 0 &&
         (!residual || ((g.ldr & 3) == 0 && (reinterpret_cast<size_t>(residual) & 15) == 0)) && !sigmoid_last && !g.gn_part && !g.bn_part && (reinterpret_cast<size_t>(out) & 15) == 0) {
@@ -1713,7 +1716,7 @@ int launch_conv(const ConvGeom& g, const float* src0, const float* src1, const f
     const char* se = knob("PIDM_CONV_SPLIT");
     const bool on = !(se && !atoi(se));
     const int mode = (g.nph == 4) ? 1 : 2;
-    if (on && split_shape_ok2(g) && g.soc == 1 && (g.C0 % 16 == 0) && ((g.ld0 | g.ld1) & 3) == 0 && (g.C1 == 0 || g.ld1 == g.ld0) &&
+    if (on && !g.wrap && split_shape_ok2(g) && g.soc == 1 && (g.C0 % 16 == 0) && ((g.ld0 | g.ld1) & 3) == 0 && (g.C1 == 0 || g.ld1 == g.ld0) &&
         g.Wv >= 8 && (mode == 1 ? (g.in_step == 2 && 2 * g.Wv == g.Wi && 2 * g.Hv == g.Hi) : (g.os == 2 && g.Wv == g.Wi && g.Hv == g.Hi)) &&
         !sigmoid_last && !g.gn_part && !g.bn_part && (g.sox & 3) == 0 && (reinterpret_cast<size_t>(out) & 15) == 0 &&
         (reinterpret_cast<size_t>(src0) & 15) == 0 && (!src1 || (reinterpret_cast<size_t>(src1) & 15) == 0) &&
@@ -1806,7 +1809,9 @@ int launch_conv(const ConvGeom& g, const float* src0, const float* src1, const f
       int n_cu = ce ? atoi(ce) : 256;
       if (n_cu < 1) n_cu = 256;
       const bool small = !retile_bm(&g8, 256) || g8.tiles_m * (g.Cout / 32) < n_cu;
-      for (int pass = 0; pass < 2; ++pass) {
+      // (circular padding: the row-streaming kernel above wraps its addresses; conv3x3_split_kernel stages a zeroed halo and has no
+      // wrapping variant - those levels go on to the fp32-MFMA kernels)
+      for (int pass = 0; pass < (g.wrap ? 0 : 2); ++pass) {
         const int nw = (small != (pass == 1)) ? 4 : 8;
         if (force && force != nw) continue;
         gs = g;
@@ -1861,13 +1866,40 @@ int launch_conv(const ConvGeom& g, const float* src0, const float* src1, const f
 }
 
 // geometry of the forward op described by a public pidm_conv_desc
+// padding mode of a geometry (pidm_conv_desc::pad_mode: 0 zeros, 1 circular).  Wrapping is an AND with extent - 1: both input
+// extents must be powers of two, and no tap may reach further than one period outside the image.  Convolutions without padding
+// (1x1) have nothing to wrap and keep the zero-mode kernels.
+int geom_set_wrap(ConvGeom* g, int pad_mode) {
+  g->wrap = 0;
+  if (pad_mode == 0) return 0;
+  if (pad_mode != 1) return fail("conv: unknown padding mode %d (0 zeros, 1 circular)", pad_mode);
+  int reach = 0;   // furthest distance of a tap from the image, in input pixels
+  for (int z = 0; z < g->nz; ++z) {
+    if (g->pad_y[z] > reach) reach = g->pad_y[z];
+    if (g->pad_x[z] > reach) reach = g->pad_x[z];
+    const int hi_y = (g->Hv - 1) * g->stride + g->KH - 1 - g->pad_y[z] - (g->Hi - 1);
+    const int hi_x = (g->Wv - 1) * g->stride + g->KW - 1 - g->pad_x[z] - (g->Wi - 1);
+    if (hi_y > reach) reach = hi_y;
+    if (hi_x > reach) reach = hi_x;
+  }
+  if (g->nph > 1) reach = 1;   // phased 4x4 / stride 2 / pad 1: input rows -1 .. Hi
+  if (reach <= 0) return 0;
+  if (!is_pow2(g->Hi) || !is_pow2(g->Wi)) return fail("conv: circular padding needs power-of-two extents (got %dx%d)", g->Hi, g->Wi);
+  if (reach > g->Hi || reach > g->Wi)
+    return fail("conv: circular padding of %d wraps around a %dx%d input more than once", reach, g->Hi, g->Wi);
+  g->wrap = 1;
+  return 0;
+}
+
 int geom_fwd(const pidm_conv_desc* d, ConvGeom* g) {
   if (d->transposed) {
     if (d->KH != 4 || d->KW != 4 || d->stride != 2 || d->pad != 1) return fail("transposed conv: only 4x4 s2 p1");
-    return make_geom(g, 1, d->B, d->Hi, d->Wi, d->C0, d->C1, d->ld0, d->ld1, d->Cout, 4, 4, 2, 1, d->out_nchw, d->ldo, d->ldo);
+    if (make_geom(g, 1, d->B, d->Hi, d->Wi, d->C0, d->C1, d->ld0, d->ld1, d->Cout, 4, 4, 2, 1, d->out_nchw, d->ldo, d->ldo)) return -1;
+    return geom_set_wrap(g, d->pad_mode);
   }
-  return make_geom(g, 0, d->B, d->Hi, d->Wi, d->C0, d->C1, d->ld0, d->ld1, d->Cout, d->KH, d->KW, d->stride, d->pad,
-                   d->out_nchw, d->ldo, d->ldo);
+  if (make_geom(g, 0, d->B, d->Hi, d->Wi, d->C0, d->C1, d->ld0, d->ld1, d->Cout, d->KH, d->KW, d->stride, d->pad,
+                d->out_nchw, d->ldo, d->ldo)) return -1;
+  return geom_set_wrap(g, d->pad_mode);
 }
 
 // geometry of the adjoint (dgrad) problem: input = dy [B,Ho,Wo,Cout] (stride ld_dy), output = dx [B,Hi,Wi,Cin] (stride ld_dx)
@@ -1875,16 +1907,19 @@ int geom_dgrad(const pidm_conv_desc* d, int ld_dy, int ld_dx, ConvGeom* g, int* 
   const int Cin = d->C0 + d->C1;
   if (d->transposed) {
     *pack_kind = 4;
-    return make_geom(g, 0, d->B, 2 * d->Hi, 2 * d->Wi, d->Cout, 0, ld_dy, 0, Cin, 4, 4, 2, 1, 0, ld_dx, ld_dx);
+    if (make_geom(g, 0, d->B, 2 * d->Hi, 2 * d->Wi, d->Cout, 0, ld_dy, 0, Cin, 4, 4, 2, 1, 0, ld_dx, ld_dx)) return -1;
+    return geom_set_wrap(g, d->pad_mode);
   }
   const int Ho = (d->Hi + 2 * d->pad - d->KH) / d->stride + 1, Wo = (d->Wi + 2 * d->pad - d->KW) / d->stride + 1;
   if (d->stride == 1) {
     *pack_kind = 2;
-    return make_geom(g, 0, d->B, Ho, Wo, d->Cout, 0, ld_dy, 0, Cin, d->KH, d->KW, 1, d->KH - 1 - d->pad, 0, ld_dx, ld_dx);
+    if (make_geom(g, 0, d->B, Ho, Wo, d->Cout, 0, ld_dy, 0, Cin, d->KH, d->KW, 1, d->KH - 1 - d->pad, 0, ld_dx, ld_dx)) return -1;
+    return geom_set_wrap(g, d->pad_mode);
   }
   if (d->stride == 2 && d->KH == 4 && d->KW == 4 && d->pad == 1) {
     *pack_kind = 3;
-    return make_geom(g, 1, d->B, Ho, Wo, d->Cout, 0, ld_dy, 0, Cin, 4, 4, 2, 1, 0, ld_dx, ld_dx);
+    if (make_geom(g, 1, d->B, Ho, Wo, d->Cout, 0, ld_dy, 0, Cin, 4, 4, 2, 1, 0, ld_dx, ld_dx)) return -1;
+    return geom_set_wrap(g, d->pad_mode);
   }
   return fail("dgrad: unsupported conv geometry");
 }

@@ -32,7 +32,9 @@ static constexpr int kAblate = PIDM_ABLATE_FLAGS;
 // ---------------------------------------------------------------------------------------------------
 // forward / dgrad kernel
 // ---------------------------------------------------------------------------------------------------
-template <int KC, int NT>
+// WRAP (circular padding, ConvGeom::wrap): a halo pixel outside the image reads the pixel at the index wrapped modulo the (power of
+// two) extent instead of zero; a compile-time variant, the zero-padding instantiations are unchanged
+template <int KC, int NT, bool WRAP = false>
 __global__ void __launch_bounds__(256) conv_igemm_kernel(ConvGeom g, int tgs, int sigmoid_last,
                                                          const float* __restrict__ src0, const float* __restrict__ src1,
                                                          const float* __restrict__ wp, const float* __restrict__ bias,
@@ -85,13 +87,13 @@ __global__ void __launch_bounds__(256) conv_igemm_kernel(ConvGeom g, int tgs, in
     // ---- stage the input tile (with halo) for channels [c0, c0+KC): one wave per halo row ----
     for (int rrow = wave; rrow < rows; rrow += 4) {
       const int img = rrow / g.IHt, hy = rrow - img * g.IHt;
-      const int b = b0 + img, iy = iy0 + hy;
+      const int b = b0 + img, iy = WRAP ? ((iy0 + hy) & (g.Hi - 1)) : iy0 + hy;
       const bool rowvalid = (b < g.B) && (iy >= 0) && (iy < g.Hi);
       const size_t rowpix = ((size_t)b * g.Hi + iy) * g.Wi;
       float* arow_s = As + (size_t)rrow * g.IWt * KCP;
       for (int e = lane; e < rowf4; e += 64) {
         const int hx = e / Q, q = e % Q;
-        const int ix = ix0 + hx, c = c0 + 4 * q;
+        const int ix = WRAP ? ((ix0 + hx) & (g.Wi - 1)) : ix0 + hx, c = c0 + 4 * q;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (rowvalid && ix >= 0 && ix < g.Wi && c < g.Cin) {
           const size_t pix = rowpix + ix;
@@ -174,7 +176,7 @@ __global__ void __launch_bounds__(256) conv_igemm_kernel(ConvGeom g, int tgs, in
 // spend most of a workgroup's life in its prologue/epilogue with the matrix pipe idle (PMC: 45 % MFMA busy).
 // MT = m-tiles (32 pixels each) per wave: MT == 2 is the 256-pixel workgroup tile (two independent accumulator chains per
 // wave, half the barriers / weight staging / B-fragment reads per MFMA).
-template <int KC, int NT, int AMAX, int BMAX, int KH, int KW, bool PHASED, bool PERSIST, int MT>
+template <int KC, int NT, int AMAX, int BMAX, int KH, int KW, bool PHASED, bool PERSIST, int MT, bool WRAP = false>
 __global__ void __launch_bounds__(256) conv_igemm_pipe_kernel(ConvGeom g, int sigmoid_last, const float* __restrict__ src0,
                                                               const float* __restrict__ src1, const float* __restrict__ wp,
                                                               const float* __restrict__ bias,
@@ -234,7 +236,9 @@ __global__ void __launch_bounds__(256) conv_igemm_pipe_kernel(ConvGeom g, int si
         const int hp = e / Q;                                                                                      \
         const int hrow = fast_div(hp, g.IWt, g.mIWt), hx = hp - hrow * g.IWt;                                      \
         const int img = fast_div(hrow, g.IHt, g.mIHt), hy = hrow - img * g.IHt;                                    \
-        const int b = p_b0 + img, iy = iy0__ + hy, ix = ix0 + hx;                                                  \
+        const int b = p_b0 + img;                                                                                  \
+        const int iy = WRAP ? ((iy0__ + hy) & (g.Hi - 1)) : iy0__ + hy;                                            \
+        const int ix = WRAP ? ((ix0 + hx) & (g.Wi - 1)) : ix0 + hx;                                                \
         if (PHASED) {                                                                                              \
           a_pix[k] = (img << 20) | (hy << 10) | hx;   /* the source pixel depends on the K-phase */                \
         } else if (b < g.B && iy >= 0 && iy < g.Hi && ix >= 0 && ix < g.Wi) {                                      \
@@ -275,8 +279,9 @@ __global__ void __launch_bounds__(256) conv_igemm_pipe_kernel(ConvGeom g, int si
       if (PHASED) {                                                                                                \
         if (a_lds[k] >= 0) {                                                                                       \
           const int b = p_b0 + (a_pix[k] >> 20);                                                                   \
-          const int iy = (p_vy0 - g.ph_pad_y[ph__] + ((a_pix[k] >> 10) & 1023)) * g.in_step + g.ph_oy[ph__];       \
-          const int ix = ((a_pix[k] & 1023) - g.ph_pad_x[ph__]) * g.in_step + g.ph_ox[ph__];                       \
+          int iy = (p_vy0 - g.ph_pad_y[ph__] + ((a_pix[k] >> 10) & 1023)) * g.in_step + g.ph_oy[ph__];             \
+          int ix = ((a_pix[k] & 1023) - g.ph_pad_x[ph__]) * g.in_step + g.ph_ox[ph__];                             \
+          if (WRAP) { iy &= g.Hi - 1; ix &= g.Wi - 1; }                                                            \
           if (b < g.B && iy >= 0 && iy < g.Hi && ix >= 0 && ix < g.Wi)                                             \
             ra[k] = *reinterpret_cast<const f32x4*>(sp__ + (((size_t)b * g.Hi + iy) * g.Wi + ix) * ld__ + 4 * aq); \
         }                                                                                                          \
@@ -530,6 +535,9 @@ __global__ void __launch_bounds__(256) conv_igemm_pipe_kernel(ConvGeom g, int si
 // tap loop done, after the barrier
 static __device__ unsigned long long g_stream_trace_fp32[4 * 64];   // (this kernel's stamps are no longer exported: pidm_debug_stream_trace reads the split-form kernels')
 
+// WRAP (circular padding): the halo rows are the image's own rows at the wrapped index, and the two halo columns - zero and written
+// once otherwise - are re-written every stage by the threads that stage pixel x = W - 1 (column 0) and x = 0 (column W + 1) of the row
+template <bool WRAP>
 __global__ void __launch_bounds__(256) conv3x3_stream_kernel(ConvGeom g, int sigmoid_last, const float* __restrict__ src0,
                                                              const float* __restrict__ src1, const float* __restrict__ wp,
                                                              const float* __restrict__ bias, const float* __restrict__ residual,
@@ -565,6 +573,7 @@ __global__ void __launch_bounds__(256) conv3x3_stream_kernel(ConvGeom g, int sig
   const int AS = SEG >> 5;                           // <= 8 slots
   const int wv8 = __builtin_amdgcn_readfirstlane(wave) * 8;
   int a_lds[8];
+  int a_lds2[WRAP ? 8 : 1];                          // WRAP: the slot's second destination (a halo column, or the dump location)
   unsigned a_vo[2];                                  // byte offset of (x, channel quad) inside a row, by slot parity
   int s_img[8], s_hy[8];                             // wave-uniform: image and halo row of this wave's segment in slot k
 #pragma unroll
@@ -576,6 +585,10 @@ __global__ void __launch_bounds__(256) conv3x3_stream_kernel(ConvGeom g, int sig
     // bookkeeping - but land in the 16 bytes of row padding, which nothing reads
     a_lds[k] = (k < AS) ? ((img * g.IHt + hy) * g.IWt + x + 1) * KCP + 4 * aq : ((tid >> 3) % npixA) * KCP + 32;
     if (k < 2) a_vo[k] = (unsigned)(x * g.ld0 + 4 * aq) * 4u;
+    if constexpr (WRAP) {
+      const int edge = (x == 0) ? g.Wv : (x == g.Wv - 1) ? -g.Wv : 0;   // pixel 0 is also column W + 1, pixel W - 1 also column 0
+      a_lds2[k] = (k < AS && edge) ? a_lds[k] + edge * KCP : ((tid >> 3) % npixA) * KCP + 32;
+    }
     const int srw = (wv8 + 32 * k) >> g.wsh;
     s_img[k] = fast_div(srw, g.IHt, g.mIHt);
     s_hy[k] = srw - s_img[k] * g.IHt;
@@ -584,7 +597,7 @@ __global__ void __launch_bounds__(256) conv3x3_stream_kernel(ConvGeom g, int sig
   const unsigned b_vo = (unsigned)((tid >> 3) * T * CinP + 4 * aq) * 4u;   // + (k * CinP + n0 * T * CinP + c0) * 4 as a scalar
 
   // zero halo columns of both buffers (and the whole pad region of unused rows stays untouched: never read)
-  for (int e = tid; e < 2 * g.NI * g.IHt * 2 * 8; e += 256) {
+  for (int e = tid; e < (WRAP ? 0 : 2 * g.NI * g.IHt * 2 * 8); e += 256) {
     const int q = e & 7, side = (e >> 3) & 1, row = (e >> 4) % (g.NI * g.IHt), bufi = (e >> 4) / (g.NI * g.IHt);
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     *reinterpret_cast<f32x4*>(smem + (size_t)bufi * bufsz + (size_t)(row * g.IWt + (side ? g.IWt - 1 : 0)) * KCP + 4 * q) = zero4;
@@ -612,7 +625,7 @@ __global__ void __launch_bounds__(256) conv3x3_stream_kernel(ConvGeom g, int sig
   {                                                                                                                \
     /* unconditional load (a branch around it makes the compiler's vmcnt bookkeeping wait for this stage's loads): */ \
     /* padding rows read row 0 of the source and are zeroed with a scalar-conditioned select when they go to LDS */  \
-    const int b__ = l_b0 + s_img[k_], iy__ = l_iy0 + s_hy[k_];                                                     \
+    const int b__ = l_b0 + s_img[k_], iy__ = WRAP ? ((l_iy0 + s_hy[k_]) & (g.Hi - 1)) : l_iy0 + s_hy[k_];         \
     const bool ok__ = (b__ < g.B) & (iy__ >= 0) & (iy__ < g.Hi);        /* wave-uniform */                         \
     const size_t row__ = ok__ ? (size_t)(b__ * g.Hi + iy__) * g.Wi : 0;                                            \
     ra[k_] = *reinterpret_cast<const f32x4*>(l_sp + row__ * (size_t)g.ld0 * 4 + a_vo[(k_) & 1]);                   \
@@ -623,6 +636,7 @@ __global__ void __launch_bounds__(256) conv3x3_stream_kernel(ConvGeom g, int sig
   {                                                                                                                \
     const float keep__ = ((amask >> (k_)) & 1u) ? 1.f : 0.f;        /* scalar */                                   \
     *reinterpret_cast<f32x4*>((buf_) + a_lds[k_]) = ra[k_] * keep__;                                               \
+    if constexpr (WRAP) *reinterpret_cast<f32x4*>((buf_) + a_lds2[k_]) = ra[k_] * keep__;                          \
   }
 #define PIDM_ST_WRITE_B(k_, buf_) *reinterpret_cast<f32x4*>((buf_) + b_lds0 + (k_)*32 * KCP) = rb[k_];
 
@@ -784,16 +798,17 @@ static int launch_conv_t(ConvGeom g, const float* src0, const float* src1, const
   if (aligned && khw_ok && nA <= amax_eff * 256 && lds_pipe <= 80 * 1024) {
     if (prof) prof_begin_launch(0, flops, st);
     const dim3 grid(g.tiles_m * tiles_n, 1, g.nz);
-#define PIDM_LAUNCH_PIPE(KH_, KW_, PH_, PS_, MT_, AMAX_, grid_)                                                                                \
+#define PIDM_LAUNCH_PIPE(KH_, KW_, PH_, PS_, MT_, AMAX_, grid_) PIDM_LAUNCH_PIPE_W(KH_, KW_, PH_, PS_, MT_, AMAX_, false, grid_)
+#define PIDM_LAUNCH_PIPE_W(KH_, KW_, PH_, PS_, MT_, AMAX_, WR_, grid_)                                                                                \
   {                                                                                                                        \
     constexpr int BMAXk = (KH_ * KW_ * BN * Q + 255) / 256;                                                                \
     static bool attr_pipe = false;                                                                                         \
     if (!attr_pipe) {                                                                                                      \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_pipe_kernel<KC, NT, AMAX_, BMAXk, KH_, KW_, PH_, PS_, MT_>), \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_pipe_kernel<KC, NT, AMAX_, BMAXk, KH_, KW_, PH_, PS_, MT_, WR_>), \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);                                    \
       attr_pipe = true;                                                                                                    \
     }                                                                                                                      \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_igemm_pipe_kernel<KC, NT, AMAX_, BMAXk, KH_, KW_, PH_, PS_, MT_>), grid_, dim3(256), \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_igemm_pipe_kernel<KC, NT, AMAX_, BMAXk, KH_, KW_, PH_, PS_, MT_, WR_>), grid_, dim3(256), \
                        lds_pipe, st, g, sigmoid_last, src0, src1 ? src1 : src0, wp, bias, residual, out);                 \
   }
     if constexpr (NT == 4 || KC == 32) {
@@ -801,7 +816,8 @@ static int launch_conv_t(ConvGeom g, const float* src0, const float* src1, const
       // convolutions
       if constexpr (KC == 32 && NT == 1) {
         if (g.KH == 3 && g.KW == 3 && g.nph == 1) {
-          PIDM_LAUNCH_PIPE(3, 3, false, false, 1, 9, grid)
+          if (g.wrap) PIDM_LAUNCH_PIPE_W(3, 3, false, false, 1, 9, true, grid)
+          else PIDM_LAUNCH_PIPE(3, 3, false, false, 1, 9, grid)
           if (prof) prof_end_launch(st);
           PIDM_CHECK_LAUNCH("conv_igemm_pipe_kernel");
           return 0;
@@ -809,6 +825,11 @@ static int launch_conv_t(ConvGeom g, const float* src0, const float* src1, const
       }
       if (g.KH != 1 || g.KW != 1 || g.nph != 1) return fail("conv: internal error - 1x1-only tile configuration on a %dx%d conv", g.KH, g.KW);
       PIDM_LAUNCH_PIPE(1, 1, false, false, 1, AMAX, grid)
+    } else if (g.wrap && g.KH > 1) {
+      // circular padding: the plain pipelined tile (the persistent and 256-pixel variants have no wrapping instantiation)
+      if (g.KH == 3) PIDM_LAUNCH_PIPE_W(3, 3, false, false, 1, AMAX, true, grid)
+      else if (g.nph > 1) PIDM_LAUNCH_PIPE_W(2, 2, true, false, 1, AMAX, true, grid)
+      else PIDM_LAUNCH_PIPE_W(2, 2, false, false, 1, AMAX, true, grid)
     } else {
       if (g.KH == 3) {
         // persistent walk when the launch has more tiles than resident workgroup slots: 2 workgroups per CU, each
@@ -854,6 +875,7 @@ static int launch_conv_t(ConvGeom g, const float* src0, const float* src1, const
       else PIDM_LAUNCH_PIPE(1, 1, false, false, 1, AMAX, grid)
     }
 #undef PIDM_LAUNCH_PIPE
+#undef PIDM_LAUNCH_PIPE_W
     if (prof) prof_end_launch(st);
     PIDM_CHECK_LAUNCH("conv_igemm_pipe_kernel");
     return ((g.gn_part || g.bn_part) && NT == 4) ? 1 : 0;   // 1: convolution done, the requested GroupNorm partials were NOT produced
@@ -876,9 +898,15 @@ static int launch_conv_t(ConvGeom g, const float* src0, const float* src1, const
   if (!attr_done) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<KC, NT>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<KC, NT, true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
     attr_done = true;
   }
   if (prof) prof_begin_launch(0, flops, st);
+  if (g.wrap)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_igemm_kernel<KC, NT, true>), dim3(g.tiles_m * tiles_n, 1, g.nz), dim3(256), lds, st, g,
+                       tgs, sigmoid_last, src0, src1 ? src1 : src0, wp, bias, residual, out);
+  else
   hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_igemm_kernel<KC, NT>), dim3(g.tiles_m * tiles_n, 1, g.nz), dim3(256), lds, st, g,
                      tgs, sigmoid_last, src0, src1 ? src1 : src0, wp, bias, residual, out);
   if (prof) prof_end_launch(st);
@@ -917,7 +945,8 @@ int launch_conv_fp32(const ConvGeom& g, const float* src0, const float* src1, co
       const bool prof = prof_enabled();
       static bool attr_s = false;
       if (!attr_s) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_stream_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_stream_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_stream_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
         attr_s = true;
       }
       ConvGeom gs = g;
@@ -928,8 +957,12 @@ int launch_conv_fp32(const ConvGeom& g, const float* src0, const float* src1, co
       if (n_cu < 1) n_cu = 256;
       const int ipw = cdiv(n_items, n_cu), wgs = cdiv(n_items, ipw);
       if (prof) prof_begin_launch(0, 2.0 * g.B * g.Hv * g.Wv * (double)g.Cout * g.Kw * 9, st);
-      hipLaunchKernelGGL(conv3x3_stream_kernel, dim3(wgs), dim3(256), lds, st, gs, sigmoid_last, src0, src1 ? src1 : src0, wp, bias, residual, out,
-                         n_items, ipw, knob("PIDM_STREAM_TRACE") ? 1 : 0);
+      if (g.wrap)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_stream_kernel<true>), dim3(wgs), dim3(256), lds, st, gs, sigmoid_last, src0, src1 ? src1 : src0, wp, bias,
+                           residual, out, n_items, ipw, knob("PIDM_STREAM_TRACE") ? 1 : 0);
+      else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_stream_kernel<false>), dim3(wgs), dim3(256), lds, st, gs, sigmoid_last, src0, src1 ? src1 : src0, wp, bias,
+                           residual, out, n_items, ipw, knob("PIDM_STREAM_TRACE") ? 1 : 0);
       if (prof) prof_end_launch(st);
       PIDM_CHECK_LAUNCH("conv3x3_stream_kernel");
       return 0;

@@ -43,7 +43,18 @@ namespace pidm {
 #endif
 // PIDM_RS_TRACE=1: shader-clock and 100 MHz real-time stamps of workgroup 0 / wave 0 around its row loop (launch_conv_rs prints the
 // clock the kernel ran at and the cycles per row)
+// The instantiations of one padding mode are a translation unit: this file compiles the zero-padding kernels and launch_conv_rs;
+// k_conv_rs_wrap.hip includes it with PIDM_CONV_RS_WRAP_TU defined and compiles the circular ones (conv3x3_rs_kernel<..., true>) and
+// launch_conv_rs_wrap, so that the two halves - each minutes of straight-line code for the compiler - build side by side.
+#ifdef PIDM_CONV_RS_WRAP_TU
+static constexpr bool kRsTuWrap = true;
+static __device__ unsigned long long g_rs_trace[4];   // (this unit's own stamps: launch_conv_rs_wrap reads them back itself)
+#define PIDM_RS_LAUNCH launch_conv_rs_wrap
+#else
+static constexpr bool kRsTuWrap = false;
 __device__ unsigned long long g_rs_trace[4];
+#define PIDM_RS_LAUNCH launch_conv_rs
+#endif
 static constexpr int kRsRow = 112;                  // bytes per LDS weight row (k_conv.hip: kSplitRow)
 static constexpr int kRsSlab = 9 * 32 * kRsRow;     // pre-split weights of one (n-tile, 16-channel chunk)
 static constexpr unsigned kRsOob = 0x80000000u;     // a byte offset no tensor reaches (the launcher checks): reads as 0
@@ -94,7 +105,10 @@ __host__ __device__ constexpr int rs_piece(int k, int bnp) {
 // One wave per SIMD (512 registers): what overlaps the matrix instructions is this wave's own vector work, interleaved by the
 // compiler inside each fenced group - so the row code has NO branch: optional operands (residual, GroupNorm partials) go through
 // buffer descriptors of size 0 when absent (loads return 0, stores are dropped), lane predicates through out-of-range offsets.
-template <int NCH, int NT, int RM, int BNP>
+// WRAP = circular padding (ConvGeom::wrap): the column left of x = 0 / right of x = W - 1 and the row above / below the image are the
+// pixels at the wrapped index (W, H powers of two) instead of out-of-range offsets - the same loads from another address; a
+// compile-time variant, the zero-padding instantiations are unchanged.
+template <int NCH, int NT, int RM, int BNP, bool WRAP = false>
 __global__ void __launch_bounds__(256) PIDM_WAVES_PER_SIMD(1)
 conv3x3_rs_kernel(ConvGeom g, const float* __restrict__ src0, const float* __restrict__ src1, const unsigned short* __restrict__ ws,
                   const float* __restrict__ bias, const float* __restrict__ residual, float* __restrict__ out, int R, int n_units,
@@ -159,7 +173,7 @@ conv3x3_rs_kernel(ConvGeom g, const float* __restrict__ src0, const float* __res
   unsigned voff[3];
 #pragma unroll
   for (int kx = 0; kx < 3; ++kx) {
-    const int x = x0 + l31 + kx - 1;
+    const int x = WRAP ? ((x0 + l31 + kx - 1) & (g.Wv - 1)) : x0 + l31 + kx - 1;
     voff[kx] = (live && x >= 0 && x < g.Wv) ? (unsigned)x * ldb + 32u * (unsigned)half : kRsOob;
   }
   const unsigned img_off = (unsigned)b * (unsigned)g.Hi * (unsigned)g.Wi * ldb, row_b = (unsigned)g.Wi * ldb;
@@ -185,7 +199,7 @@ conv3x3_rs_kernel(ConvGeom g, const float* __restrict__ src0, const float* __res
   // loads of input row index i_ (image row y0 - 1 + i_) into raw[kx_][ch_]; rows outside the image or past the strip read zeros
 #define PIDM_RSF_LOAD(i_, kx_, ch_)                                                                                   \
   {                                                                                                                   \
-    const int r__ = y0 - 1 + (i_);                                                                                    \
+    const int r__ = WRAP ? ((y0 - 1 + (i_)) & (g.Hi - 1)) : y0 - 1 + (i_);                                            \
     const bool ok__ = (r__ >= 0) & (r__ < g.Hi) & ((i_) < R + 2);                                                     \
     const unsigned vo__ = ok__ ? voff[kx_] : kRsOob;                                                                  \
     const unsigned so__ = img_off + (unsigned)(ok__ ? r__ : 0) * row_b;                                               \
@@ -469,8 +483,15 @@ static int rs_fwd_knob(const char* name, int dflt) {
 }
 
 // 0: launched; 1: not this kernel's shape (the caller goes on); < 0: error
-int launch_conv_rs(const ConvGeom& g, const float* src0, const float* src1, const unsigned short* wsplit, const float* bias,
+#ifndef PIDM_CONV_RS_WRAP_TU
+int launch_conv_rs_wrap(const ConvGeom& g, const float* src0, const float* src1, const unsigned short* wsplit, const float* bias,
+                        const float* residual, float* out, hipStream_t st);   // k_conv_rs_wrap.hip: the same launcher over the WRAP kernels
+#endif
+int PIDM_RS_LAUNCH(const ConvGeom& g, const float* src0, const float* src1, const unsigned short* wsplit, const float* bias,
                    const float* residual, float* out, hipStream_t st) {
+#ifndef PIDM_CONV_RS_WRAP_TU
+  if (g.wrap) return launch_conv_rs_wrap(g, src0, src1, wsplit, bias, residual, out, st);
+#endif
   if (!rs_fwd_knob("PIDM_CONV_RS", 1)) return 1;
   if (!(g.KH == 3 && g.KW == 3 && g.stride == 1 && g.nz == 1 && g.nph == 1 && g.os == 1 && g.pad_y[0] == 1 && g.pad_x[0] == 1)) return 1;
   if (!(g.Wv == g.Wi && g.Hv == g.Hi && g.Ho == g.Hv && g.Wo == g.Wv && (g.Wv % 32) == 0 && g.Wv >= 32)) return 1;
@@ -505,7 +526,7 @@ int launch_conv_rs(const ConvGeom& g, const float* src0, const float* src1, cons
   // after a fall-through writes Ho*Wo/32 chunks per image)
   if (g.gn_part || g.bn_part) *g.part_chunks_out = pch;
   if (knob("PIDM_TRACE_CONV"))
-    fprintf(stderr, "[pidm]   -> conv3x3_rs_kernel<%d, %d, %d, %d>, %d strips of %d rows, %d n-groups, %zu B LDS\n", NCH, NT, R % 3, bnp, n_units, R, ngr, lds);
+    fprintf(stderr, "[pidm]   -> conv3x3_rs_kernel<%d, %d, %d, %d%s>, %d strips of %d rows, %d n-groups, %zu B LDS\n", NCH, NT, R % 3, bnp, kRsTuWrap ? ", circular" : "", n_units, R, ngr, lds);
   const bool prof = prof_enabled();
   if (prof) prof_begin_launch(2, 2.0 * g.B * g.Hv * g.Wv * (double)g.Cout * g.Cin * 9, st);
   const dim3 grid(cdiv(n_units, 4), ngr), block(256);
@@ -518,16 +539,17 @@ int launch_conv_rs(const ConvGeom& g, const float* src0, const float* src1, cons
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) trace = 0;
   }
-#define PIDM_RSF_GO(a, b, c, d)                                                                                                   \
+#define PIDM_RSF_GO(a, b, c, d) PIDM_RSF_GO5(a, b, c, d, kRsTuWrap)
+#define PIDM_RSF_GO5(a, b, c, d, w)                                                                                                   \
   {                                                                                                                               \
     static bool attr__ = false;                                                                                                   \
     if (!attr__) {                                                                                                                \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_rs_kernel<a, b, c, d>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256); \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_rs_kernel<a, b, c, d, w>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256); \
       attr__ = true;                                                                                                              \
     }                                                                                                                             \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_rs_kernel<a, b, c, d>), grid, block, lds, st, g, src0, s1, wsplit, bias, residual, out, R, n_units, sb, rb, pch, trace); \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_rs_kernel<a, b, c, d, w>), grid, block, lds, st, g, src0, s1, wsplit, bias, residual, out, R, n_units, sb, rb, pch, trace); \
   }
-#define PIDM_RSF_GO_RM(a, b, d) if (R % 3 == 1) PIDM_RSF_GO(a, b, 1, d) else PIDM_RSF_GO(a, b, 2, d)
+#define PIDM_RSF_GO_RM(a, b, d) if (R % 3 == 1) { PIDM_RSF_GO(a, b, 1, d) } else { PIDM_RSF_GO(a, b, 2, d) }
   if (NCH == 2 && NT == 2) PIDM_RSF_GO_RM(2, 2, 0)
   else if (NCH == 2 && bnp) PIDM_RSF_GO_RM(2, 1, 1)
   else if (NCH == 2) PIDM_RSF_GO_RM(2, 1, 0)
@@ -535,6 +557,7 @@ int launch_conv_rs(const ConvGeom& g, const float* src0, const float* src1, cons
   else PIDM_RSF_GO_RM(4, 1, 0)
 #undef PIDM_RSF_GO_RM
 #undef PIDM_RSF_GO
+#undef PIDM_RSF_GO5
   if (prof) prof_end_launch(st);
   PIDM_CHECK_LAUNCH("conv3x3_rs_kernel");
   if (trace) {
@@ -548,9 +571,11 @@ int launch_conv_rs(const ConvGeom& g, const float* src0, const float* src1, cons
 
 }  // namespace pidm
 
+#ifndef PIDM_CONV_RS_WRAP_TU
 // measurement aid: the four stamps the last traced launch of conv3x3_rs_kernel left (PIDM_RS_TRACE=1): shader-clock counter and
 // 100 MHz real-time counter of workgroup 0 / wave 0 before and after its row loop
 extern "C" int pidm_debug_conv_rs_trace(unsigned long long* out4) {
   if (!out4) return pidm::fail("debug_conv_rs_trace: null argument");
   return hipMemcpyFromSymbol(out4, HIP_SYMBOL(pidm::g_rs_trace), sizeof(unsigned long long) * 4) == hipSuccess ? 0 : -1;
 }
+#endif

@@ -29,7 +29,9 @@ static const int kBM = 128;  // pixels per workgroup tile (as k_conv.hip)
 // ---------------------------------------------------------------------------------------------------
 // (struct WgradGeom: pidm_common.h - shared with k_wgrad_rs.hip)
 
-template <int MAXT>
+// WRAP (all LDS-staged kernels of this file but the split form): circular padding - a halo pixel outside the image is the pixel at
+// the index wrapped modulo the power-of-two extent (ConvGeom::wrap); a compile-time variant, the zero-padding code is unchanged
+template <int MAXT, bool WRAP = false>
 __global__ void __launch_bounds__(256) conv_wgrad_kernel(WgradGeom wg, const float* __restrict__ src0,
                                                          const float* __restrict__ src1, const float* __restrict__ dy,
                                                          float* __restrict__ partial, float* __restrict__ bias_partial) {
@@ -73,13 +75,13 @@ __global__ void __launch_bounds__(256) conv_wgrad_kernel(WgradGeom wg, const flo
     __syncthreads();
     for (int rrow = wave; rrow < rows; rrow += 4) {
       const int img = rrow / g.IHt, hy = rrow - img * g.IHt;
-      const int b = b0 + img, iy = iy0 + hy;
+      const int b = b0 + img, iy = WRAP ? ((iy0 + hy) & (g.Hi - 1)) : iy0 + hy;
       const bool rowvalid = (b < g.B) && (iy >= 0) && (iy < g.Hi);
       const size_t rowpix = ((size_t)b * g.Hi + iy) * g.Wi;
       float* xrow_s = Xs + (size_t)rrow * g.IWt * 32;
       for (int e = lane; e < rowf4; e += 64) {
         const int hx = e >> 3, q = e & 7;
-        const int ix = ix0 + hx, c = n0 + 4 * q;
+        const int ix = WRAP ? ((ix0 + hx) & (g.Wi - 1)) : ix0 + hx, c = n0 + 4 * q;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (rowvalid && ix >= 0 && ix < g.Wi && c < g.Cin) {
           const size_t pix = rowpix + ix;
@@ -176,7 +178,7 @@ __global__ void __launch_bounds__(256) conv_wgrad_kernel(WgradGeom wg, const flo
 // zeroed once, whole image rows staged with wave-uniform validity and scalar row bases, per-thread constant offsets.  The fp32
 // MFMA shares the SIMD's vector ALUs, so the ~350 VALU instructions of the per-tile slot decode cost a quarter of a tile's 144
 // MFMAs (measured: 75 TFLOP/s on the 3x3 weight gradients before).
-template <int KH, int KW, bool PHASED, bool WIDE, int MINW, bool ROWST = false>
+template <int KH, int KW, bool PHASED, bool WIDE, int MINW, bool ROWST = false, bool WRAP = false>
 __global__ void __launch_bounds__(256, MINW) conv_wgrad_pipe_kernel(WgradGeom wg, const float* __restrict__ src0,
                                                               const float* __restrict__ src1, const float* __restrict__ dy,
                                                               float* __restrict__ partial, float* __restrict__ bias_partial) {
@@ -210,6 +212,7 @@ __global__ void __launch_bounds__(256, MINW) conv_wgrad_pipe_kernel(WgradGeom wg
   f32x4 rx[XMAX], ry[YMAX];
   // ---- ROWST state: per-thread constants and wave-uniform row descriptors ----
   int rs_lds[8];
+  int rs_lds2[(ROWST && WRAP) ? 8 : 1];   // WRAP: the halo column a slot's pixel is also written to (x = 0 -> column W + 1, x = W - 1 -> column 0), -1: none
   unsigned rs_xvo[2], rs_yvo = 0, rs_xmask = 0, rs_ymask = 0;
   int rs_img[8], rs_hy[8], rs_yimg[4];
   int rs_AS = 0;
@@ -223,6 +226,10 @@ __global__ void __launch_bounds__(256, MINW) conv_wgrad_pipe_kernel(WgradGeom wg
       const int img = fast_div(sr, g.IHt, g.mIHt), hy = sr - img * g.IHt;
       rs_lds[k] = (k < rs_AS) ? ((img * g.IHt + hy) * g.IWt + x + 1) * 32 + 4 * q : -1;
       if (k < 2) rs_xvo[k] = (unsigned)(x * xld + 4 * q) * 4u;
+      if constexpr (WRAP) {
+        const int edge = (x == 0) ? g.Wv : (x == g.Wv - 1) ? -g.Wv : 0;
+        rs_lds2[k] = (k < rs_AS && edge) ? rs_lds[k] + edge * 32 : -1;
+      }
       const int srw = (wv8 + 32 * k) >> g.wsh;
       rs_img[k] = fast_div(srw, g.IHt, g.mIHt);
       rs_hy[k] = srw - rs_img[k] * g.IHt;
@@ -230,8 +237,8 @@ __global__ void __launch_bounds__(256, MINW) conv_wgrad_pipe_kernel(WgradGeom wg
     rs_yvo = (unsigned)((tid >> 3) * wg.ld_dy + cy) * 4u;
 #pragma unroll
     for (int k = 0; k < 4; ++k) rs_yimg[k] = (wv8 + 32 * k) >> (g.wsh + g.tsh);
-    // halo columns of the X tile: zero for every tile, written once
-    for (int e = tid; e < g.NI * g.IHt * 2 * 8; e += 256) {
+    // halo columns of the X tile: zero for every tile, written once (WRAP: re-written with every tile, below)
+    for (int e = tid; e < (WRAP ? 0 : g.NI * g.IHt * 2 * 8); e += 256) {
       const int qq = e & 7, side = (e >> 3) & 1, row = e >> 4;
       *reinterpret_cast<f32x4*>(Xs + (size_t)(row * g.IWt + (side ? g.IWt - 1 : 0)) * 32 + 4 * qq) = f32x4{0.f, 0.f, 0.f, 0.f};
     }
@@ -242,7 +249,8 @@ __global__ void __launch_bounds__(256, MINW) conv_wgrad_pipe_kernel(WgradGeom wg
     const int tile__ = (tile_);                                                                                   \
     const int b0__ = (tile__ / tpi) * g.NI, vy0__ = (tile__ % tpi) * g.TH;                                        \
     _Pragma("unroll") for (int k = 0; k < 8; ++k) {                                                               \
-      const int b__ = b0__ + rs_img[k], iy__ = vy0__ - g.pad_y[0] + rs_hy[k];                                     \
+      const int b__ = b0__ + rs_img[k];                                                                           \
+      const int iy__ = WRAP ? ((vy0__ - g.pad_y[0] + rs_hy[k]) & (g.Hi - 1)) : vy0__ - g.pad_y[0] + rs_hy[k];     \
       const bool ok__ = (b__ < g.B) & (iy__ >= 0) & (iy__ < g.Hi) & cx_ok;                                         \
       const size_t row__ = ok__ ? (size_t)(b__ * g.Hi + iy__) * g.Wi : 0;                                         \
       rx[k] = *reinterpret_cast<const f32x4*>(rs_xsrc + row__ * (size_t)xld * 4 + rs_xvo[k & 1]);                 \
@@ -271,6 +279,7 @@ __global__ void __launch_bounds__(256, MINW) conv_wgrad_pipe_kernel(WgradGeom wg
         const int b = b0__ + img;                                                                                 \
         int iy = iy0__ + hy, ix = ix0__ + hx;                                                                     \
         if (PHASED) { iy = iy * g.in_step + g.ph_oy[ph]; ix = ix * g.in_step + g.ph_ox[ph]; }                      \
+        if (WRAP) { iy &= g.Hi - 1; ix &= g.Wi - 1; }                                                             \
         if (b < g.B && iy >= 0 && iy < g.Hi && ix >= 0 && ix < g.Wi)                                               \
           rx[k] = *reinterpret_cast<const f32x4*>(xsrc + (((size_t)b * g.Hi + iy) * g.Wi + ix) * xld);            \
       }                                                                                                           \
@@ -303,7 +312,12 @@ __global__ void __launch_bounds__(256, MINW) conv_wgrad_pipe_kernel(WgradGeom wg
     if constexpr (ROWST) {
 #pragma unroll
       for (int k = 0; k < 8; ++k)
-        if (k < rs_AS) *reinterpret_cast<f32x4*>(Xs + rs_lds[k]) = rx[k] * (((rs_xmask >> k) & 1u) ? 1.f : 0.f);
+        if (k < rs_AS) {
+          *reinterpret_cast<f32x4*>(Xs + rs_lds[k]) = rx[k] * (((rs_xmask >> k) & 1u) ? 1.f : 0.f);
+          if constexpr (WRAP) {
+            if (rs_lds2[k] >= 0) *reinterpret_cast<f32x4*>(Xs + rs_lds2[k]) = rx[k] * (((rs_xmask >> k) & 1u) ? 1.f : 0.f);
+          }
+        }
 #pragma unroll
       for (int k = 0; k < YMAX; ++k)
         *reinterpret_cast<f32x4*>(Ys + (size_t)((tid >> 3) + 32 * k) * 32 + 4 * q) = ry[k] * (((rs_ymask >> k) & 1u) ? 1.f : 0.f);
@@ -632,7 +646,7 @@ __global__ void __launch_bounds__(768) conv_wgrad_split_kernel(WgradGeom wg, con
 // the flattened (tap, channel) index - 98 columns for 7x7x2 instead of 49 taps x a 32-channel tile that is 94 % padding.
 // Wave w owns n-tiles {w, w+4, ...} (<= MAXN) and walks the whole 128-pixel tile; lane j of an n-tile reads
 // X[halo(p) + tap_j][c_j] straight from the LDS halo tile.
-template <int MAXN>
+template <int MAXN, bool WRAP = false>
 __global__ void __launch_bounds__(256) conv_wgrad_smallc_kernel(WgradGeom wg, const float* __restrict__ src0,
                                                                 const float* __restrict__ dy, float* __restrict__ partial,
                                                                 float* __restrict__ bias_partial) {
@@ -674,7 +688,7 @@ __global__ void __launch_bounds__(256) conv_wgrad_smallc_kernel(WgradGeom wg, co
     for (int e = tid; e < npixA * Cin; e += 256) {
       const int c = e % Cin, hp = e / Cin;
       const int hx = hp % g.IWt, hy = (hp / g.IWt) % g.IHt, img = hp / (g.IWt * g.IHt);
-      const int b = b0 + img, iy = iy0 + hy, ix = ix0 + hx;
+      const int b = b0 + img, iy = WRAP ? ((iy0 + hy) & (g.Hi - 1)) : iy0 + hy, ix = WRAP ? ((ix0 + hx) & (g.Wi - 1)) : ix0 + hx;
       float v = 0.f;
       if (b < g.B && iy >= 0 && iy < g.Hi && ix >= 0 && ix < g.Wi) v = src0[(((size_t)b * g.Hi + iy) * g.Wi + ix) * g.ld0 + c];
       Xs[e] = v;
@@ -1515,6 +1529,7 @@ static bool launch_wgrad_split(const WgradGeom& plan, const float* src0, const f
   const ConvGeom& g = plan.g;
   const char* se = knob("PIDM_WGRAD_SPLIT");
   if (se && !atoi(se)) return false;
+  if (g.wrap) return false;   // conv_wgrad_split_kernel stages zeroed halo elements: no wrapping variant
   if (!(g.KH == 3 && g.KW == 3 && g.stride == 1 && g.nph == 1 && g.nz == 1 && g.pad_y[0] == 1 && g.pad_x[0] == 1 && g.Wv == g.Wi &&
         g.Hv == g.Hi && g.Wv >= 8 && (g.Cin % 32 == 0) && (g.C0 % 32 == 0) && (g.Cout % 32 == 0) && (g.C1 == 0 || g.ld1 == g.ld0) &&
         (g.ld0 & 3) == 0 && (ld_dy & 3) == 0 && (reinterpret_cast<size_t>(src0) & 15) == 0 &&
@@ -1584,6 +1599,8 @@ int launch_wgrad(const ConvGeom& g, const float* src0, const float* src1, const 
   if (!attr_done) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<9>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<9, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
     attr_done = true;
   }
   const bool prof = prof_enabled();
@@ -1607,10 +1624,16 @@ int launch_wgrad(const ConvGeom& g, const float* src0, const float* src1, const 
     if (!attr_s) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_smallc_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_smallc_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_smallc_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_smallc_kernel<4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
       attr_s = true;
     }
     if (lds2 > 96 * 1024) return fail("wgrad(small-C): tile needs %zu B of LDS", lds2);
-    if (maxn <= 1)
+    if (g.wrap && maxn <= 1)
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_wgrad_smallc_kernel<1, true>), grid2, dim3(256), lds2, st, wg, src0, dy, partial, bias_partial);
+    else if (g.wrap)
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_wgrad_smallc_kernel<4, true>), grid2, dim3(256), lds2, st, wg, src0, dy, partial, bias_partial);
+    else if (maxn <= 1)
       hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_wgrad_smallc_kernel<1>), grid2, dim3(256), lds2, st, wg, src0, dy, partial, bias_partial);
     else
       hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_wgrad_smallc_kernel<4>), grid2, dim3(256), lds2, st, wg, src0, dy, partial, bias_partial);
@@ -1621,14 +1644,19 @@ int launch_wgrad(const ConvGeom& g, const float* src0, const float* src1, const 
     const dim3 gridp(wg.nsplit, (wg.MP / 32) * (wg.NP / 32), 4);
 #define PIDM_LAUNCH_WG6(KH_, KW_, PH_, WIDE_, MINW_, ROWST_, grid_)                                                        \
   {                                                                                                                        \
+    if (g.wrap && (KH_) > 1) PIDM_LAUNCH_WG7(KH_, KW_, PH_, WIDE_, MINW_, ROWST_, ((KH_) > 1), grid_)                        \
+    else PIDM_LAUNCH_WG7(KH_, KW_, PH_, WIDE_, MINW_, ROWST_, false, grid_)                                                 \
+  }
+#define PIDM_LAUNCH_WG7(KH_, KW_, PH_, WIDE_, MINW_, ROWST_, WR_, grid_)                                                        \
+  {                                                                                                                        \
     static bool attr_ = false;                                                                                             \
     if (!attr_) {                                                                                                          \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_pipe_kernel<KH_, KW_, PH_, WIDE_, MINW_, ROWST_>), \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_pipe_kernel<KH_, KW_, PH_, WIDE_, MINW_, ROWST_, WR_>), \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);                                    \
       attr_ = true;                                                                                                        \
     }                                                                                                                      \
     PIDM_PROF_NAME("conv_wgrad_pipe_kernel");                                                                              \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_wgrad_pipe_kernel<KH_, KW_, PH_, WIDE_, MINW_, ROWST_>), grid_, dim3(256), lds, st, wg, \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_wgrad_pipe_kernel<KH_, KW_, PH_, WIDE_, MINW_, ROWST_, WR_>), grid_, dim3(256), lds, st, wg, \
                        src0, src1 ? src1 : src0, dy, partial, bias_partial);                                              \
   }
 #define PIDM_LAUNCH_WG(KH_, KW_, PH_, WIDE_, MINW_, grid_) PIDM_LAUNCH_WG6(KH_, KW_, PH_, WIDE_, MINW_, false, grid_)
@@ -1720,7 +1748,12 @@ int launch_wgrad(const ConvGeom& g, const float* src0, const float* src1, const 
     }
 #undef PIDM_LAUNCH_WG
 #undef PIDM_LAUNCH_WG6
-  } else if (wg.tgs == 1)
+#undef PIDM_LAUNCH_WG7
+  } else if (g.wrap && wg.tgs == 1)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_wgrad_kernel<1, true>), grid, dim3(256), lds, st, wg, src0, src1 ? src1 : src0, dy, partial, bias_partial);
+  else if (g.wrap)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_wgrad_kernel<9, true>), grid, dim3(256), lds, st, wg, src0, src1 ? src1 : src0, dy, partial, bias_partial);
+  else if (wg.tgs == 1)
     hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_wgrad_kernel<1>), grid, dim3(256), lds, st, wg, src0, src1 ? src1 : src0, dy, partial, bias_partial);
   else
     hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_wgrad_kernel<9>), grid, dim3(256), lds, st, wg, src0, src1 ? src1 : src0, dy, partial, bias_partial);
@@ -1780,7 +1813,7 @@ using namespace pidm;
 extern "C" size_t pidm_conv_wgrad_ws(const pidm_conv_desc* d) {
   ConvGeom g;
   if (d->transposed) {
-    if (make_geom(&g, 0, d->B, 2 * d->Hi, 2 * d->Wi, d->Cout, 0, d->Cout, 0, d->C0 + d->C1, 4, 4, 2, 1, 0, 4, 4)) return 0;
+    if (make_geom(&g, 0, d->B, 2 * d->Hi, 2 * d->Wi, d->Cout, 0, d->Cout, 0, d->C0 + d->C1, 4, 4, 2, 1, 0, 4, 4) || geom_set_wrap(&g, d->pad_mode)) return 0;
   } else if (geom_fwd(d, &g)) {
     return 0;
   }
@@ -1796,7 +1829,7 @@ extern "C" int pidm_conv_wgrad(const pidm_conv_desc* d, const float* src0, const
   if (d->transposed) {
     // swapped operands: X' = dy [B,2H,2W,Cout], dY' = x [B,H,W,Cin]; result [Cin][Cout][4][4]
     if (d->C1) return fail("wgrad: transposed conv with two sources is not supported");
-    if (make_geom(&g, 0, d->B, 2 * d->Hi, 2 * d->Wi, d->Cout, 0, ld_dy, 0, d->C0, 4, 4, 2, 1, 0, 4, 4)) return -1;
+    if (make_geom(&g, 0, d->B, 2 * d->Hi, 2 * d->Wi, d->Cout, 0, ld_dy, 0, d->C0, 4, 4, 2, 1, 0, 4, 4) || geom_set_wrap(&g, d->pad_mode)) return -1;
     rc = launch_wgrad(g, dy, nullptr, src0, d->ld0, dw_ref, nullptr, workspace, st);
     dy_rows = (size_t)d->B * 4 * d->Hi * d->Wi;
   } else {

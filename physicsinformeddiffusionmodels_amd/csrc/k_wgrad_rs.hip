@@ -92,6 +92,9 @@ constexpr unsigned kRsInv = 0x80000000u;   // a byte offset no tensor reaches (t
 
 // The body of the kernel: problem `wg` (by value in scalar registers: kernel arguments of the single-problem kernel, a row of the
 // device table of the grouped one), workgroup (split, by) of its splits x blocks grid.
+// WRAP = circular padding (family kWgFamRsWrap): the row above / below the image and the pixel left of x = 0 / right of x = W - 1
+// are the pixels at the wrapped index instead of out-of-range offsets; a compile-time variant, the zero-padding body is unchanged.
+template <bool WRAP>
 __device__ __forceinline__ void conv_wgrad_rs_body(const WgradItem& wg, const int split, const int by, float* __restrict__ red) {
   const float* __restrict__ src0 = wg.src0;
   const float* __restrict__ src1 = wg.src1;
@@ -137,18 +140,32 @@ __device__ __forceinline__ void conv_wgrad_rs_body(const WgradItem& wg, const in
     // which is never dereferenced (its loads get kRsInv)
     unsigned offx = ((unsigned)(b * H + r0 - 1) << wsh) * ldxb + (unsigned)x0 * ldxb + (unsigned)l31 * 4u;
     unsigned offy = ((unsigned)(b * H + r0) << wsh) * ldyb + (unsigned)x0 * ldyb + (unsigned)l31 * 4u;
+    // WRAP: (image b, row 0, pixel x0, this lane's channel); the row's offset is added per load from the wrapped row index
+    const unsigned offx_img = ((unsigned)(b * H) << wsh) * ldxb + (unsigned)x0 * ldxb + (unsigned)l31 * 4u;
     int yx = r0 - 1;          // image row the next X load reads
     int ny = 0;               // dY rows of the chunk loaded so far
 
     float rawx[2][10], rawy[2][8];
 #define PIDM_RS_LOAD_X(dst_)                                                                                        \
   {                                                                                                                 \
+    if constexpr (WRAP) {                                                                                           \
+      /* (the range check covers the per-lane offset only: the wrapped neighbours get their whole offset there) */  \
+      const bool ok__ = s_ok & (yx <= r0 + R);                                                                      \
+      const unsigned ox__ = offx_img + ((unsigned)(yx & (H - 1)) << wsh) * ldxb;                                    \
+      const unsigned vc__ = ok__ ? ox__ : kRsInv;                                                                   \
+      const unsigned vp__ = ok__ ? (left_ok ? ox__ - ldxb : ox__ + (unsigned)(W - 1) * ldxb) : kRsInv;              \
+      const unsigned vn__ = ok__ ? (right_ok ? ox__ + 8u * ldxb : ox__ - (unsigned)(W - 8) * ldxb) : kRsInv;        \
+      dst_[0] = pidm_buf_load_f32(rx, vp__, 0u);                                                                    \
+      _Pragma("unroll") for (int j__ = 0; j__ < 8; ++j__) dst_[1 + j__] = pidm_buf_load_f32(rx, vc__, (unsigned)j__ * ldxb); \
+      dst_[9] = pidm_buf_load_f32(rx, vn__, 0u);                                                                    \
+    } else {                                                                                                        \
     const bool ok__ = s_ok & (yx >= 0) & (yx < H) & (yx <= r0 + R);                                                 \
     const unsigned vc__ = ok__ ? offx : kRsInv, vp__ = (ok__ & left_ok) ? offx - ldxb : kRsInv,                     \
                    vn__ = (ok__ & right_ok) ? offx : kRsInv;                                                        \
     dst_[0] = pidm_buf_load_f32(rx, vp__, 0u);                                                                      \
     _Pragma("unroll") for (int j__ = 0; j__ < 8; ++j__) dst_[1 + j__] = pidm_buf_load_f32(rx, vc__, (unsigned)j__ * ldxb); \
     dst_[9] = pidm_buf_load_f32(rx, vn__, 8u * ldxb);                                                               \
+    }                                                                                                               \
     offx += rowxb;                                                                                                  \
     ++yx;                                                                                                           \
   }
@@ -240,15 +257,17 @@ __device__ __forceinline__ void conv_wgrad_rs_body(const WgradItem& wg, const in
   }
 }
 
+template <bool WRAP>
 __global__ void __launch_bounds__(256) conv_wgrad_rs_kernel(WgradItem wg) {
   HIP_DYNAMIC_SHARED(float, red)      // epilogue only: [4 waves][9 taps][32 dY channels][32 X channels]
-  conv_wgrad_rs_body(wg, (int)blockIdx.x, (int)blockIdx.y, red);
+  conv_wgrad_rs_body<WRAP>(wg, (int)blockIdx.x, (int)blockIdx.y, red);
 }
 
 // The same for a TABLE of problems in one launch (round 5; WgradQueue, pidm_launch.h): workgroup blockIdx.x + blk_base belongs to the
 // problem whose [blk0, blk0 + gx * gy) contains it - one load per lane and a ballot (the table has at most 64 rows) - and runs that
 // problem's workgroup (local % gx, local / gx).  Consecutive workgroups of one problem still read neighbouring splits; the
 // launch has no boundary between problems, so the chip drains once per flush instead of once per problem.
+template <bool WRAP>
 __global__ void __launch_bounds__(256) conv_wgrad_rs_multi_kernel(const WgradItem* __restrict__ table, int n, unsigned blk_base) {
   HIP_DYNAMIC_SHARED(float, red)
   const unsigned bid = blockIdx.x + blk_base;
@@ -258,7 +277,7 @@ __global__ void __launch_bounds__(256) conv_wgrad_rs_multi_kernel(const WgradIte
   const int p = __builtin_amdgcn_readfirstlane(__popcll(__ballot(bid >= first_)) - 1);
   const WgradItem wg = table[p];
   const unsigned local = bid - wg.blk0;
-  conv_wgrad_rs_body(wg, (int)(local % wg.gx), (int)(local / wg.gx), red);
+  conv_wgrad_rs_body<WRAP>(wg, (int)(local % wg.gx), (int)(local / wg.gx), red);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -596,7 +615,7 @@ static void rs4_plan(WgradGeom* wg, int nsplit) {
 bool wgrad_rs4_eligible(const ConvGeom& g, int ld_dy) {
   auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
   const size_t pix_x = (size_t)g.B * g.Hi * g.Wi, pix_y = (size_t)g.B * g.Hv * g.Wv;
-  return g.nph == 4 && g.nz == 1 && g.KH == 2 && g.KW == 2 && g.in_step == 2 && 2 * g.Wv == g.Wi && 2 * g.Hv == g.Hi && g.Wv >= 8 &&
+  return !g.wrap && g.nph == 4 && g.nz == 1 && g.KH == 2 && g.KW == 2 && g.in_step == 2 && 2 * g.Wv == g.Wi && 2 * g.Hv == g.Hi && g.Wv >= 8 &&
          pow2(g.Wv) && pow2(g.Hv) && (g.Cin % 32 == 0) && (g.C0 % 32 == 0) && (g.Cout % 32 == 0) && (g.C1 == 0 || g.ld1 == g.ld0) &&
          pix_x * (size_t)g.ld0 * 4 < 0x7ff00000ull && pix_y * (size_t)ld_dy * 4 < 0x7ff00000ull;
 }
@@ -643,7 +662,7 @@ bool wgrad_rs7_eligible(const ConvGeom& g, int ld_dy) {
   auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
   const size_t pix = (size_t)g.B * g.Hi * g.Wi;
   const int NJ = g.KH * g.KW * g.Cin;
-  return g.nph == 1 && g.nz == 1 && g.C1 == 0 && g.stride == 1 && g.Cin <= 16 && g.KH * g.KW > 1 && NJ <= 16 * 32 && g.Wv == g.Wi &&
+  return !g.wrap && g.nph == 1 && g.nz == 1 && g.C1 == 0 && g.stride == 1 && g.Cin <= 16 && g.KH * g.KW > 1 && NJ <= 16 * 32 && g.Wv == g.Wi &&
          g.Hv == g.Hi && g.Wi >= 8 && pow2(g.Wi) && pow2(g.Hi) && (g.Cout % 32 == 0) && pix * (size_t)g.ld0 * 4 < 0x7ff00000ull &&
          pix * (size_t)ld_dy * 4 < 0x7ff00000ull;
 }
@@ -725,6 +744,7 @@ bool wgrad_rs_queueable(const ConvGeom& g, const float* src0, const float* dy, i
   const char* off = knob("PIDM_WGRAD_RS");
   if (off && !atoi(off)) return false;
   auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
+  // (circular padding, ConvGeom::wrap: the wrapping body, queued in a family of its own - kWgFamRsWrap)
   if (!(g.KH == 3 && g.KW == 3 && g.stride == 1 && g.nph == 1 && g.nz == 1 && g.pad_y[0] == 1 && g.pad_x[0] == 1 && g.Wv == g.Wi &&
         g.Hv == g.Hi && g.Wi >= 8 && pow2(g.Wi) && pow2(g.Hi) && (g.Cin % 32 == 0) && (g.C0 % 32 == 0) && (g.Cout % 32 == 0) &&
         (g.C1 == 0 || g.ld1 == g.ld0) && (reinterpret_cast<size_t>(src0) & 3) == 0 && (reinterpret_cast<size_t>(dy) & 3) == 0))
@@ -755,8 +775,10 @@ bool launch_wgrad_rs(const WgradGeom& plan, const float* src0, const float* src1
   const WgradItem it = wgrad_item(wg, src0, src1, dy, partial, bias_partial, (unsigned)ns, (unsigned)((wg.MP / 32) * (wg.NP / 32)), 0);
   static bool attr_ = false;
   if (!attr_) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_rs_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRsWgradLds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_rs_multi_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRsWgradLds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_rs_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRsWgradLds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_rs_multi_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRsWgradLds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_rs_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRsWgradLds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_rs_multi_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRsWgradLds);
     attr_ = true;
   }
   if (knob("PIDM_TRACE_CONV"))
@@ -764,11 +786,12 @@ bool launch_wgrad_rs(const WgradGeom& plan, const float* src0, const float* src1
             wg.nsplit, it.gy, wg.rs_S, wg.rs_R, wg.rs_ppw);
   *used = wg;
   if (wq) {
-    wq->push(kWgFamRs, it, 2.0 * g.B * g.Hv * g.Wv * (double)g.Cout * g.Cin * 9);
+    wq->push(g.wrap ? kWgFamRsWrap : kWgFamRs, it, 2.0 * g.B * g.Hv * g.Wv * (double)g.Cout * g.Cin * 9);
     return true;
   }
   PIDM_PROF_NAME("conv_wgrad_rs_kernel");
-  hipLaunchKernelGGL(conv_wgrad_rs_kernel, dim3(it.gx, it.gy, 1), dim3(256), kRsWgradLds, st, it);
+  if (g.wrap) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_wgrad_rs_kernel<true>), dim3(it.gx, it.gy, 1), dim3(256), kRsWgradLds, st, it);
+  else hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_wgrad_rs_kernel<false>), dim3(it.gx, it.gy, 1), dim3(256), kRsWgradLds, st, it);
   return true;
 }
 
@@ -776,8 +799,16 @@ bool launch_wgrad_rs(const WgradGeom& plan, const float* src0, const float* src1
 int launch_wgrad_rs_multi(const WgradItem* table_dev, int first, int n, unsigned blk_base, unsigned nblocks, hipStream_t st) {
   if (n <= 0 || nblocks == 0) return 0;
   PIDM_PROF_NAME("conv_wgrad_rs_multi_kernel");
-  hipLaunchKernelGGL(conv_wgrad_rs_multi_kernel, dim3(nblocks), dim3(256), kRsWgradLds, st, table_dev + first, n, blk_base);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_wgrad_rs_multi_kernel<false>), dim3(nblocks), dim3(256), kRsWgradLds, st, table_dev + first, n, blk_base);
   PIDM_CHECK_LAUNCH("conv_wgrad_rs_multi_kernel");
+  return 0;
+}
+
+static int launch_wgrad_rs_wrap_multi(const WgradItem* table_dev, int first, int n, unsigned blk_base, unsigned nblocks, hipStream_t st) {
+  if (n <= 0 || nblocks == 0) return 0;
+  PIDM_PROF_NAME("conv_wgrad_rs_multi_kernel<circular>");
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_wgrad_rs_multi_kernel<true>), dim3(nblocks), dim3(256), kRsWgradLds, st, table_dev + first, n, blk_base);
+  PIDM_CHECK_LAUNCH("conv_wgrad_rs_multi_kernel<circular>");
   return 0;
 }
 
@@ -791,6 +822,7 @@ int launch_wgrad_rs4_multi(const WgradItem* table_dev, int first, int n, unsigne
 
 int launch_wgrad_multi(int fam, const WgradItem* table_dev, int first, int n, unsigned blk_base, unsigned nblocks, hipStream_t st) {
   return fam == kWgFamRs    ? launch_wgrad_rs_multi(table_dev, first, n, blk_base, nblocks, st)
+         : fam == kWgFamRsWrap ? launch_wgrad_rs_wrap_multi(table_dev, first, n, blk_base, nblocks, st)
          : fam == kWgFamRs4 ? launch_wgrad_rs4_multi(table_dev, first, n, blk_base, nblocks, st)
          : fam == kWgFam1x1Split ? launch_wgrad_1x1_split_multi(table_dev, first, n, blk_base, nblocks, st)
                             : launch_wgrad_1x1_multi(table_dev, first, n, blk_base, nblocks, st);

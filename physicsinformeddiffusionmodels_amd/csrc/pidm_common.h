@@ -242,6 +242,8 @@ struct ConvGeom {
   int tiles_m;       // number of 128-pixel tiles
   int tpw;           // persistent conv kernels: consecutive m-tiles walked by one workgroup (0/1: one tile per workgroup)
   int rpad;          // split-form 3x3 kernels: extra bytes per halo-tile row in LDS (bank spreading at the 8- / 16-wide levels)
+  int wrap;          // 1: circular padding - a tap outside the image reads the pixel at the index wrapped modulo the (power-of-two)
+                     // extent instead of zero; only kernels with a wrapping variant may take such a geometry (launch_conv, launch_wgrad)
   int xcd;           // split-form kernels: workgroup -> work-item order that follows the XCDs (split_vblock, k_conv.hip); 0: off
   // GroupNorm statistics of the OUTPUT from the epilogue (k_norm.hip consumes them): per (image, 32-pixel wave chunk, group)
   // sum and sum of squares as doubles at gn_part[((b*gn_nchunk + chunk)*gn_G + g)*2]; gn_part == null: off.
@@ -284,7 +286,8 @@ struct WgradGeom {
 // Only the fields the grouped kernels read (no host pointers, no padding: tables of these are compared with memcmp).  Three kernel
 // families, one table and one launch each: the 3x3 / stride-1 row-streaming kernel, its 4x4 / stride-2 sibling (k_wgrad_rs.hip)
 // and the three 1x1 pixel-stream kernels (k_conv_wgrad.hip; `kind` says which).
-enum { kWgFamRs = 0, kWgFamRs4 = 1, kWgFam1x1 = 2, kWgFam1x1Split = 3, kWgFams = 4 };   // (1x1Split: the wide-operand 1x1 problems on the bf16 pipe, round 6)
+enum { kWgFamRs = 0, kWgFamRs4 = 1, kWgFam1x1 = 2, kWgFam1x1Split = 3, kWgFamRsWrap = 4, kWgFams = 5 };   // (1x1Split: the wide-operand 1x1 problems on the bf16 pipe, round 6;
+                                                                                                            //  RsWrap: the 3x3 row-streaming problems with circular padding)
 enum { kWgKindStream = 0, kWgKindStream4Dy = 1, kWgKindStream4X = 2 };
 struct WgradItem {
   const float* src0;

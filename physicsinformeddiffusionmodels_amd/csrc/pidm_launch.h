@@ -90,6 +90,7 @@ int launch_split_reduce(const float* partial, float* dst, const float* bias_part
 int make_geom(ConvGeom* g, int kind, int B, int Hi, int Wi, int C0, int C1, int ld0, int ld1, int Cout, int KH, int KW,
               int stride, int pad, int out_nchw, int ldo, int ldr);
 int geom_dgrad(const pidm_conv_desc* d, int ld_dy, int ld_dx, ConvGeom* g, int* pack_kind);
+int geom_set_wrap(ConvGeom* g, int pad_mode);          // ConvGeom::wrap from a pidm_conv_desc::pad_mode (checks the extents)
 int geom_fwd(const pidm_conv_desc* d, ConvGeom* g);   // geometry of the forward op described by a public pidm_conv_desc
 // re-tile a stride-1 geometry for a bm-pixel workgroup tile (bm = 256: two m-tiles per wave)
 inline bool retile_bm(ConvGeom* g, int bm) {

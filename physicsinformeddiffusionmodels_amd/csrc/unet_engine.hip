@@ -40,6 +40,7 @@ struct ConvLayer {
   int C0 = 0, C1 = 0, Cout = 0, K = 1, stride = 1, pad = 0, transposed = 0, H = 1;
   size_t off_f = 0, off_d = 0;  // float offsets into the packed-weight region
   bool dgrad = true;
+  int pad_mode = 0;             // 0 zeros, 1 circular (pidm_unet_cfg::padding_mode; forward, input and weight gradient alike)
 };
 
 struct ResBlock {
@@ -298,12 +299,22 @@ static pidm_conv_desc desc_of(const ConvLayer& L, int B) {
   memset(&d, 0, sizeof(d));
   d.B = B; d.Hi = L.H; d.Wi = L.H; d.C0 = L.C0; d.C1 = L.C1; d.ld0 = L.C0; d.ld1 = L.C1; d.Cout = L.Cout;
   d.KH = d.KW = L.K; d.stride = L.stride; d.pad = L.pad; d.transposed = L.transposed; d.out_nchw = 0; d.ldo = L.Cout;
+  d.pad_mode = L.pad_mode;
   return d;
 }
 
 static int geom_fwd_layer(const ConvLayer& L, int B, int out_nchw, ConvGeom* g) {
-  if (L.transposed) return make_geom(g, 1, B, L.H, L.H, L.C0, L.C1, L.C0, L.C1, L.Cout, 4, 4, 2, 1, out_nchw, L.Cout, L.Cout);
-  return make_geom(g, 0, B, L.H, L.H, L.C0, L.C1, L.C0, L.C1, L.Cout, L.K, L.K, L.stride, L.pad, out_nchw, L.Cout, L.Cout);
+  if (L.transposed) {
+    if (make_geom(g, 1, B, L.H, L.H, L.C0, L.C1, L.C0, L.C1, L.Cout, 4, 4, 2, 1, out_nchw, L.Cout, L.Cout)) return -1;
+  } else if (make_geom(g, 0, B, L.H, L.H, L.C0, L.C1, L.C0, L.C1, L.Cout, L.K, L.K, L.stride, L.pad, out_nchw, L.Cout, L.Cout)) {
+    return -1;
+  }
+  return geom_set_wrap(g, L.pad_mode);
+}
+// weight gradient of a transposed layer: the 4x4 / stride-2 problem with swapped operands (X' = dy, dY' = x)
+static int geom_wgrad_transposed(const ConvLayer& L, int B, int ld_dy, ConvGeom* g) {
+  if (make_geom(g, 0, B, 2 * L.H, 2 * L.H, L.Cout, 0, ld_dy, 0, L.C0, 4, 4, 2, 1, 0, 4, 4)) return -1;
+  return geom_set_wrap(g, L.pad_mode);
 }
 
 static int out_h(const ConvLayer& L) { return L.transposed ? 2 * L.H : (L.H + 2 * L.pad - L.K) / L.stride + 1; }
@@ -336,6 +347,7 @@ static void make_resblock(pidm_unet* U, ResBlock& m, const std::string& pre, int
     m.mlpb = U->index.at(pre + "mlp.1.bias");
   }
   m.c1.C0 = C0; m.c1.C1 = C1; m.c1.Cout = Co; m.c1.K = 3; m.c1.pad = 1; m.c1.H = H;
+  m.c1.pad_mode = m.c2.pad_mode = U->cfg.padding_mode;
   conv_param(U, m.c1, pre + "block1.proj", true);
   m.gn1w = add_param(U, pre + "block1.norm.weight", Co);
   m.gn1b = add_param(U, pre + "block1.norm.bias", Co);
@@ -369,6 +381,14 @@ extern "C" int pidm_unet_create(const pidm_unet_cfg* cfg, pidm_unet** out) {
   if (cfg->dim % 8 || cfg->dim < 8) return fail("unet_create: dim must be a multiple of 8");
   const int P = cfg->image_size;
   if (P <= 0 || (P & (P - 1)) || (P >> (cfg->n_levels - 1)) < 1 || P > 128) return fail("unet_create: image_size %d must be a power of two <= 128", P);
+  if (cfg->padding_mode != 0 && cfg->padding_mode != 1) return fail("unet_create: unknown padding_mode %d (0 zeros, 1 circular)", cfg->padding_mode);
+  if (cfg->padding_mode == 1) {
+    // circular padding wraps modulo the extent of a level: a level of extent 1 would wrap around more than once (the reference's
+    // F.pad refuses the same image size / level count)
+    for (int i = 0; i < cfg->n_levels; ++i)
+      if ((P >> i) < 2) return fail("unet_create: circular padding needs an extent of at least 2 at every level; level %d of a %dx%d image with %d levels is %dx%d", i, P, P, cfg->n_levels, P >> i, P >> i);
+  }
+  const int pm = cfg->padding_mode;
   pidm_unet* U = new pidm_unet();
   U->cfg = *cfg;
   U->n_lv = cfg->n_levels;
@@ -406,7 +426,7 @@ extern "C" int pidm_unet_create(const pidm_unet_cfg* cfg, pidm_unet** out) {
   for (auto& f : film) add_param(U, f.first + "mlp.1.bias", (size_t)2 * f.second);
 
   U->init_conv.C0 = cfg->channels * (cfg->self_condition ? 2 : 1); U->init_conv.Cout = dim; U->init_conv.K = cfg->init_kernel;
-  U->init_conv.pad = cfg->init_kernel / 2; U->init_conv.H = P; U->init_conv.dgrad = true;
+  U->init_conv.pad = cfg->init_kernel / 2; U->init_conv.H = P; U->init_conv.dgrad = true; U->init_conv.pad_mode = pm;
   conv_param(U, U->init_conv, "init_conv", true);
   U->lin1.C0 = dim; U->lin1.Cout = td; conv_param(U, U->lin1, "time_mlp.1", true);
   U->lin2.C0 = td; U->lin2.Cout = td; conv_param(U, U->lin2, "time_mlp.3", true);
@@ -426,7 +446,7 @@ extern "C" int pidm_unet_create(const pidm_unet_cfg* cfg, pidm_unet** out) {
     make_attn(U, U->attn[iat++], pre + "2.", dout, res[i], false);
     if (i < n - 1) {
       ConvLayer& d = U->down[i];
-      d.C0 = dout; d.Cout = dout; d.K = 4; d.stride = 2; d.pad = 1; d.H = res[i];
+      d.C0 = dout; d.Cout = dout; d.K = 4; d.stride = 2; d.pad = 1; d.H = res[i]; d.pad_mode = pm;
       conv_param(U, d, pre + "3", true);
     }
   }
@@ -443,8 +463,9 @@ extern "C" int pidm_unet_create(const pidm_unet_cfg* cfg, pidm_unet** out) {
     make_attn(U, U->attn[iat++], pre + "2.", din, res[lvl], false);
     if (j < n - 1) {
       ConvLayer& u = U->up[j];
-      u.C0 = din; u.Cout = din; u.K = 4; u.stride = 2; u.pad = 1; u.transposed = 1; u.H = res[lvl];
-      conv_param(U, u, pre + "3", true);
+      u.C0 = din; u.Cout = din; u.K = 4; u.stride = 2; u.pad = 1; u.transposed = 1; u.H = res[lvl]; u.pad_mode = pm;
+      // the reference's CircularUpsample keeps its ConvTranspose3d in a sub-module (src/unet_model.py:165-199)
+      conv_param(U, u, pm ? pre + "3.conv_transpose" : pre + "3", true);
     }
   }
   make_resblock(U, U->rb[irb], "final_conv.0.", dim, dim, dim, P, false); irb++;
@@ -970,7 +991,7 @@ static int conv_wgrad(Run& r, const ConvLayer& L, const float* x0, const float* 
   const int Ho = out_h(L);
   const hipStream_t wst = r.dry ? r.st : fork_side(r);
   if (L.transposed) {
-    if (make_geom(&g, 0, r.B, 2 * L.H, 2 * L.H, L.Cout, 0, ld_dy, 0, L.C0, 4, 4, 2, 1, 0, 4, 4)) return -1;
+    if (geom_wgrad_transposed(L, r.B, ld_dy, &g)) return -1;
     float* part = r.part_alloc(wgrad_ws_bytes(g));
     RUN(launch_wgrad(g, dy, nullptr, x0, L.C0, U->G[L.w], nullptr, part, wst, r.q(), r.wgq()));
     if (L.b >= 0) {
@@ -1197,7 +1218,7 @@ static size_t scratch_floats_needed(pidm_unet* U, int B) {
   auto conv_ws = [&](const ConvLayer& L) {
     ConvGeom g;
     if (L.transposed) {
-      if (make_geom(&g, 0, B, 2 * L.H, 2 * L.H, L.Cout, 0, L.Cout, 0, L.C0, 4, 4, 2, 1, 0, 4, 4)) return;
+      if (geom_wgrad_transposed(L, B, L.Cout, &g)) return;
     } else if (geom_fwd_layer(L, B, 0, &g)) {
       return;
     }

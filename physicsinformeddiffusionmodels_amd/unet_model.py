@@ -92,20 +92,30 @@ class _PreNorm(_Holder):
         self.norm = _ChanLayerNorm(dim)
 
 
-class _Block(_Holder):
-    def __init__(self, dim, dim_out, groups):
+class _CircularUpsample(_Holder):
+    """The reference's CircularUpsample (src/unet_model.py:171-193): its ConvTranspose3d lives in the sub-module
+    `conv_transpose`, so the state_dict keys are `ups.i.3.conv_transpose.{weight,bias}`.  The reference builds that layer
+    with padding 5 and pads the input by 2 itself; the parameter shapes and initialisation do not depend on the padding."""
+
+    def __init__(self, dim):
         super().__init__()
-        self.proj = nn.Conv3d(dim, dim_out, (1, 3, 3), padding=(0, 1, 1))
+        self.conv_transpose = nn.ConvTranspose3d(dim, dim, (1, 4, 4), (1, 2, 2), padding=(0, 5, 5))
+
+
+class _Block(_Holder):
+    def __init__(self, dim, dim_out, groups, padding_mode='zeros'):
+        super().__init__()
+        self.proj = nn.Conv3d(dim, dim_out, (1, 3, 3), padding=(0, 1, 1), padding_mode=padding_mode)
         self.norm = nn.GroupNorm(groups, dim_out)
         self.act = nn.SiLU()
 
 
 class _ResnetBlock(_Holder):
-    def __init__(self, dim, dim_out, time_emb_dim=None, groups=8):
+    def __init__(self, dim, dim_out, time_emb_dim=None, groups=8, padding_mode='zeros'):
         super().__init__()
         self.mlp = nn.Sequential(nn.SiLU(), nn.Linear(time_emb_dim, dim_out * 2)) if exists(time_emb_dim) else None
-        self.block1 = _Block(dim, dim_out, groups)
-        self.block2 = _Block(dim_out, dim_out, groups)
+        self.block1 = _Block(dim, dim_out, groups, padding_mode)
+        self.block2 = _Block(dim_out, dim_out, groups, padding_mode)
         self.res_conv = nn.Conv3d(dim, dim_out, 1) if dim != dim_out else nn.Identity()
 
 
@@ -174,8 +184,8 @@ class Unet3D(nn.Module):
         sigmoid_last_channel=False,
     ):
         super().__init__()
-        if padding_mode != 'zeros':
-            raise ValueError('Unknown padding mode: {} (the gfx950 engine implements zero padding)'.format(padding_mode))
+        if padding_mode not in ('zeros', 'circular'):
+            raise ValueError('Unknown padding mode: {}'.format(padding_mode))
         if not use_sparse_linear_attn:
             raise NotImplementedError('use_sparse_linear_attn=False is not on the accelerated path')
         self.dim = dim
@@ -203,7 +213,7 @@ class Unet3D(nn.Module):
         assert init_kernel_size % 2 == 1
         pad = init_kernel_size // 2
         self.init_conv = nn.Conv3d(self.input_channels, init_dim, (1, init_kernel_size, init_kernel_size),
-                                   padding=(0, pad, pad))
+                                   padding=(0, pad, pad), padding_mode=padding_mode)
         self.init_temporal_attn = _Wrap(_PreNorm(init_dim, temporal_attn(init_dim)))
 
         dims = [init_dim, *[dim * m for m in dim_mults]]
@@ -223,27 +233,28 @@ class Unet3D(nn.Module):
         for ind, (din, dout) in enumerate(in_out):
             last = ind >= n_res - 1
             self.downs.append(nn.ModuleList([
-                _ResnetBlock(din, dout, tdim, resnet_groups),
-                _ResnetBlock(dout, dout, tdim, resnet_groups),
+                _ResnetBlock(din, dout, tdim, resnet_groups, padding_mode),
+                _ResnetBlock(dout, dout, tdim, resnet_groups, padding_mode),
                 lin_attn(dout),
-                nn.Conv3d(dout, dout, (1, 4, 4), (1, 2, 2), (0, 1, 1)) if not last else nn.Identity(),
+                nn.Conv3d(dout, dout, (1, 4, 4), (1, 2, 2), (0, 1, 1), padding_mode=padding_mode) if not last else nn.Identity(),
             ]))
         mid = dims[-1]
-        self.mid_block1 = _ResnetBlock(mid, mid, tdim, resnet_groups)
+        self.mid_block1 = _ResnetBlock(mid, mid, tdim, resnet_groups, padding_mode)
         self.mid_spatial_attn = _Wrap(_PreNorm(mid, _Wrap(_Attention(mid, attn_heads, cond_dim=self.cond_dim))))
         self.mid_temporal_attn = _Wrap(_PreNorm(mid, temporal_attn(mid)))
-        self.mid_block2 = _ResnetBlock(mid, mid, tdim, resnet_groups)
+        self.mid_block2 = _ResnetBlock(mid, mid, tdim, resnet_groups, padding_mode)
         for ind, (din, dout) in enumerate(reversed(in_out)):
             last = ind >= n_res - 1
             self.ups.append(nn.ModuleList([
-                _ResnetBlock(dout * 2, din, tdim, resnet_groups),
-                _ResnetBlock(din, din, tdim, resnet_groups),
+                _ResnetBlock(dout * 2, din, tdim, resnet_groups, padding_mode),
+                _ResnetBlock(din, din, tdim, resnet_groups, padding_mode),
                 lin_attn(din),
-                nn.ConvTranspose3d(din, din, (1, 4, 4), (1, 2, 2), (0, 1, 1)) if not last else nn.Identity(),
+                nn.Identity() if last else (_CircularUpsample(din) if padding_mode == 'circular'
+                                            else nn.ConvTranspose3d(din, din, (1, 4, 4), (1, 2, 2), (0, 1, 1))),
             ]))
         out_dim = default(out_dim, channels)
         self.out_dim = out_dim
-        self.final_conv = nn.Sequential(_ResnetBlock(dim * 2, dim, None, resnet_groups), nn.Conv3d(dim, out_dim, 1))
+        self.final_conv = nn.Sequential(_ResnetBlock(dim * 2, dim, None, resnet_groups, padding_mode), nn.Conv3d(dim, out_dim, 1))
         self.emb_conv = nn.Sequential(nn.Conv2d(channels, init_dim, 1), nn.GELU(),
                                       nn.Conv2d(init_dim, init_dim, 3, padding=1))
         self.combine_conv = nn.Conv2d(init_dim * 2, init_dim, 1)
