@@ -223,6 +223,33 @@ size_t pidm_darcy_gen_lds_bytes(int P);
 int pidm_darcy_gen(const double* basis, const double* z, int q, const double* K_in, int P, double d0, double d1, double bc_sign,
                    const double* int_w, const double* f_s, int max_iter, double rtol, double* K_out, double* p_out,
                    double* res_mean, int32_t* iters, double* relres, int B, void* stream);
+/*   pidm_darcy_gen_acc: the same system and the same method with findiff's classed operators of order acc in {2, 4, 6}
+ *                   (src/darcy_data_generation.py:129-142, every FinDiff(..., acc=acc)): rows i < acc/2 forward, rows
+ *                   i > P-1-acc/2 backward, the others central; central and one-sided first-derivative stencils have acc+1 taps,
+ *                   one-sided second-derivative stencils acc+2.  K_0 and K_1 come from the same operators.  Arguments as
+ *                   pidm_darcy_gen, plus:
+ *                   launch protocol - one call runs at most iters_this_launch (>= 1) CGLS iterations per sample that is not done
+ *                   and returns; the caller repeats the call (first_launch = 0, every other argument unchanged) until done[b] != 0
+ *                   for every b.  first_launch != 0 initialises `state` (whatever it held).  A sample is finished when it
+ *                   converges (||S A^T r|| <= rtol ||S A^T b||) or reaches max_iter iterations in total; the launch that
+ *                   finishes it runs the deflation and the residual pass and writes p_out[b], res_mean[b], iters[b], relres[b]
+ *                   and done[b] = 1, once; later launches leave a finished sample untouched.  An unfinished sample gets
+ *                   done[b] = 0.  K_out is written by the first launch.  A solve cut into launches of any size returns bit-identical
+ *                   results to the same solve in one launch.
+ *                   state (device, pidm_darcy_gen_acc_state_bytes(P, B) bytes, 8-byte aligned), per sample 3 P^2 + 4P + 3 doubles:
+ *                   iterate | search direction | row residuals (P^2 each) | boundary residuals (4P) | gamma | gamma0 | two int32
+ *                   (iterations done, done flag).  K, K_0, K_1 and the column scales are recomputed by every launch.
+ *                   done [B] int32 (device, required).  Limits: 8 <= P <= 64 at acc 2 and 4, 10 <= P <= 64 at acc 6 (the forward
+ *                   second derivative of row 2 reaches column 9); anything else, a null state or iters_this_launch < 1 is an error.
+ *   pidm_darcy_gen_acc_lds_bytes: LDS per workgroup (four P^2 fields, 4P boundary residuals, the 3 x (acc+2) x 2 unit-spacing
+ *                   coefficient table shared by both axes, the reduction slots); the entry fails when it exceeds the 160 KB of a
+ *                   gfx950 workgroup.  0 for an order other than 2, 4, 6. */
+size_t pidm_darcy_gen_acc_state_bytes(int P, int B);
+size_t pidm_darcy_gen_acc_lds_bytes(int P, int acc);
+int pidm_darcy_gen_acc(const double* basis, const double* z, int q, const double* K_in, int P, int acc, double d0, double d1,
+                       double bc_sign, const double* int_w, const double* f_s, int max_iter, double rtol, int iters_this_launch,
+                       int first_launch, void* state, double* K_out, double* p_out, double* res_mean, int32_t* iters,
+                       double* relres, int32_t* done, int B, void* stream);
 
 /* Mechanics training-data generation      replaces nothing in the reference: it never generated its topology-optimisation samples
  * (they were downloaded); these entries supply the data main.py:90-101 expects (one [65,65,10] .npy per sample), DESIGN section 4b

@@ -4,10 +4,13 @@ The reference draws a log-permeability field from a Karhunen-Loeve expansion (KL
 dense (P^2+4P+1) x P^2 finite-difference system of -div(K grad p) = f_s with Neumann rows and an integral row, and solves it
 with `scipy.linalg.lstsq` (7.2 s per 64 x 64 sample on one CPU core).  Here the same functions keep their names and signatures,
 and the solve runs in `csrc/k_darcy_gen.hip`: one workgroup per sample, KLE synthesis and matrix-free column-scaled CGLS in
-fp64 ("Darcy data generation").  Host-side pieces are the grid, the eigendecomposition of the covariance (the
+fp64 ("Darcy data generation").  `acc` (the reference's finite-difference order, 2 / 4 / 6) selects the operators: 2 is
+that kernel; 4 and 6 run in `csrc/k_darcy_gen_acc.hip`, in launches of a bounded number of iterations that carry the CGLS state
+between them.  Host-side pieces are the grid, the eigendecomposition of the covariance (the
 reference's exact full `eigh`, cached) and the CSV writing.  There is no CPU fallback for the solve.
 
     python -m physicsinformeddiffusionmodels_amd.darcy_data_generation --n-samples 10000 --out ./data/darcy/train
+    python -m physicsinformeddiffusionmodels_amd.darcy_data_generation --n-samples 10000 --out ./data/darcy/train4 --acc 4
 """
 from __future__ import annotations
 
@@ -25,6 +28,13 @@ from ._lib import PidmError, get_lib, ptr, stream_ptr
 DEFAULTS = dict(pixels_per_dim=64, pixels_at_boundary=True, domain_length=1., length_scale=0.1, q=64, reverse_dy=True)
 RTOL = 1e-12          # ||S A^T r|| / ||S A^T b|| at which a sample counts as solved (tests/test_darcy_data_generation.py)
 MAX_ITER = 200000     # P = 64 takes ~40-50k iterations
+ACCS = (2, 4, 6)
+# max_iter=None: about twice the largest count measured at P = 64 (profiles/darcy_gen_bench_acc.txt)
+MAX_ITER_ACC = {2: MAX_ITER, 4: 1000000, 6: 4000000}     # measured maxima at P = 64, batch 256: 494 k (acc 4), 2.04 M (acc 6)
+# iterations per launch of the resumable entry for a batch of at most one workgroup per compute unit: a launch at P = 64, acc 6,
+# batch 256 then takes 0.60 s (30 us per iteration; bound: 2 s); _launch_acc divides it by
+# ceil(B / compute units)
+ITERS_PER_LAUNCH = 20000
 
 
 # ---- the reference's host functions (same names, signatures and results) ----------------------------------------------------
@@ -100,14 +110,23 @@ def z_of_seed(seed, q):
 
 # ---- the engine --------------------------------------------------------------------------------------------------------------
 
+def min_pixels(acc):
+    """Smallest grid of order acc: rows below acc/2 use forward stencils, and the second-derivative one of row acc/2 - 1 reaches
+    column 3 acc/2 (9 at acc 6); 8 below that, as the second-order kernel."""
+    return max(8, 3 * acc // 2 + 1)
+
+
 class DarcyProblem:
     """Grid-dependent, sample-independent data of the reference system: spacings, boundary sign, f_s and integral weights."""
 
-    def __init__(self, P, pixels_at_boundary=True, reverse_dy=True, domain_length=1.):
-        if not 8 <= P <= 64:
-            raise PidmError(f"darcy data generation: pixels_per_dim={P} outside [8, 64] (the solve keeps four fp64 P x P fields "
-                            f"in LDS)")
-        self.P, self.pixels_at_boundary, self.reverse_dy = P, bool(pixels_at_boundary), bool(reverse_dy)
+    def __init__(self, P, pixels_at_boundary=True, reverse_dy=True, domain_length=1., acc=2):
+        if acc not in ACCS:
+            raise PidmError(f"darcy data generation: acc={acc!r} is not one of the orders {ACCS} the gfx950 solve implements")
+        pmin = min_pixels(acc)
+        if not pmin <= P <= 64:
+            raise PidmError(f"darcy data generation: pixels_per_dim={P} outside [{pmin}, 64] at acc={acc} (a one-sided second "
+                            f"derivative of order {acc} spans {acc + 2} points; the solve keeps four fp64 P x P fields in LDS)")
+        self.P, self.pixels_at_boundary, self.reverse_dy, self.acc = P, bool(pixels_at_boundary), bool(reverse_dy), acc
         self.d0 = domain_length / (P - 1) if pixels_at_boundary else domain_length / P
         self.d1 = -self.d0 if reverse_dy else self.d0
         # y-min row: +D1 p with reverse_dy, -D1 p without (y-max the opposite), src/darcy_data_generation.py:147-150
@@ -162,7 +181,11 @@ def _check_converged(relres, rtol, labels):
         raise PidmError(f"darcy solve did not converge (||S A^T r|| / ||S A^T b|| > {rtol:g}) for sample(s) {bad}: raise max_iter")
 
 
-def _launch(lib, device, prob, *, basis=None, z=None, K_in=None, B, max_iter, rtol):
+def _launch(lib, device, prob, *, basis=None, z=None, K_in=None, B, max_iter, rtol, iters_per_launch=None, resumable=False,
+            stats=None):
+    if prob.acc != 2 or resumable:
+        return _launch_acc(lib, device, prob, basis=basis, z=z, K_in=K_in, B=B, max_iter=max_iter, rtol=rtol,
+                           iters_per_launch=iters_per_launch, stats=stats)
     P = prob.P
     f_s, int_w = prob.on(device)
     K = torch.empty(B, P * P, dtype=torch.float64, device=device)
@@ -174,17 +197,66 @@ def _launch(lib, device, prob, *, basis=None, z=None, K_in=None, B, max_iter, rt
     lib.check(lib.pidm_darcy_gen(ptr(basis), ptr(z), q, ptr(K_in), P, prob.d0, prob.d1, prob.bc_sign, ptr(int_w), ptr(f_s),
                                  int(max_iter), float(rtol), ptr(K), ptr(p), ptr(res), ptr(iters), ptr(relres), B,
                                  stream_ptr(device)), "pidm_darcy_gen")
+    if stats is not None:
+        stats.update(launches=1, longest_launch_s=None, iters_per_launch=None)
+    return K, p, res, iters, relres
+
+
+def _launch_acc(lib, device, prob, *, basis=None, z=None, K_in=None, B, max_iter, rtol, iters_per_launch=None, stats=None):
+    """The resumable entry (csrc/k_darcy_gen_acc.hip): launches of at most `iters_per_launch` iterations per sample until every
+    sample is done; the B done flags are read back after each launch.  A batch larger than the device's compute units runs its
+    workgroups one behind the other, so the budget of a launch is divided by ceil(B / compute units)."""
+    P = prob.P
+    f_s, int_w = prob.on(device)
+    if iters_per_launch is None:
+        iters_per_launch = ITERS_PER_LAUNCH
+    iters_per_launch = int(iters_per_launch)
+    if iters_per_launch < 1:
+        raise PidmError(f"darcy data generation: iters_per_launch={iters_per_launch} must be >= 1")
+    if device.type == "cuda" and B > 0:
+        cus = torch.cuda.get_device_properties(device).multi_processor_count
+        iters_per_launch = max(1, iters_per_launch // -(-B // cus))
+    iters_per_launch = min(iters_per_launch, 2 ** 31 - 1)
+    K = torch.empty(B, P * P, dtype=torch.float64, device=device)
+    p = torch.empty(B, P * P, dtype=torch.float64, device=device)
+    res = torch.empty(B, dtype=torch.float64, device=device)
+    iters = torch.empty(B, dtype=torch.int32, device=device)
+    relres = torch.empty(B, dtype=torch.float64, device=device)
+    done = torch.zeros(B, dtype=torch.int32, device=device)
+    state = torch.empty(max(1, lib.pidm_darcy_gen_acc_state_bytes(P, B) // 8), dtype=torch.float64, device=device)
+    q = 0 if z is None else z.shape[1]
+    launches, longest, first = 0, 0., 1
+    most = int(max_iter) // iters_per_launch + 2         # every launch advances every unfinished sample by iters_per_launch
+    while True:
+        t0 = time.perf_counter()
+        lib.check(lib.pidm_darcy_gen_acc(ptr(basis), ptr(z), q, ptr(K_in), P, prob.acc, prob.d0, prob.d1, prob.bc_sign, ptr(int_w),
+                                         ptr(f_s), int(max_iter), float(rtol), iters_per_launch, first, ptr(state), ptr(K), ptr(p),
+                                         ptr(res), ptr(iters), ptr(relres), ptr(done), B, stream_ptr(device)), "pidm_darcy_gen_acc")
+        finished = bool(done.cpu().all())                # (a few hundred bytes; also waits for the launch)
+        longest = max(longest, time.perf_counter() - t0)
+        launches, first = launches + 1, 0
+        if finished:
+            break
+        if launches >= most:
+            raise PidmError(f"pidm_darcy_gen_acc: samples unfinished after {launches} launches of {iters_per_launch} iterations "
+                            f"(max_iter={max_iter})")
+    if stats is not None:
+        stats.update(launches=launches, longest_launch_s=longest, iters_per_launch=iters_per_launch)
     return K, p, res, iters, relres
 
 
 def generate_darcy_batch(seeds, pixels_per_dim=64, q=64, length_scale=0.1, pixels_at_boundary=True, reverse_dy=True,
-                         domain_length=1., basis=None, max_iter=MAX_ITER, rtol=RTOL, cache_dir=None, device=None, lib=None):
-    """Samples for the given seeds: K = exp(KLE(z(seed))) and the reference's least-squares pressure p.
-    Returns (K [B,P*P], p [B,P*P], res [B], iters [B]) on the device, fp64 (res = mean |row residual| over all P^2+4P+1 rows).
-    `basis` ([q, P*P], see kle_basis) overrides the eigendecomposition."""
+                         domain_length=1., basis=None, max_iter=None, rtol=RTOL, cache_dir=None, device=None, lib=None, acc=2,
+                         iters_per_launch=None, resumable=False, stats=None):
+    """Samples for the given seeds: K = exp(KLE(z(seed))) and the reference's least-squares pressure p at finite-difference order
+    `acc` (2, 4 or 6).  Returns (K [B,P*P], p [B,P*P], res [B], iters [B]) on the device, fp64 (res = mean |row residual| over all
+    P^2+4P+1 rows).  `basis` ([q, P*P], see kle_basis) overrides the eigendecomposition.  max_iter=None: MAX_ITER_ACC[acc].
+    acc 4 and 6 (and acc 2 with resumable=True) run in launches of at most `iters_per_launch` iterations (None: ITERS_PER_LAUNCH,
+    scaled to the batch); `stats` (a dict) receives the number of launches and the longest one."""
     device, lib = _resolve(device, lib)
     P = pixels_per_dim
-    prob = DarcyProblem(P, pixels_at_boundary, reverse_dy, domain_length)
+    prob = DarcyProblem(P, pixels_at_boundary, reverse_dy, domain_length, acc)
+    max_iter = MAX_ITER_ACC[acc] if max_iter is None else max_iter
     seeds = [int(s) for s in seeds]
     if basis is None:
         basis = kle_basis(P, length_scale, q, pixels_at_boundary, cache_dir, domain_length)
@@ -194,17 +266,19 @@ def generate_darcy_batch(seeds, pixels_per_dim=64, q=64, length_scale=0.1, pixel
     q = basis.shape[0]
     z = torch.from_numpy(np.stack([z_of_seed(s, q) for s in seeds]) if seeds else np.zeros((0, q))).to(device)
     bt = torch.from_numpy(basis).to(device)
-    K, p, res, iters, relres = _launch(lib, device, prob, basis=bt, z=z.contiguous(), B=len(seeds), max_iter=max_iter, rtol=rtol)
+    K, p, res, iters, relres = _launch(lib, device, prob, basis=bt, z=z.contiguous(), B=len(seeds), max_iter=max_iter, rtol=rtol,
+                                       iters_per_launch=iters_per_launch, resumable=resumable, stats=stats)
     if device.type == "cuda":
         torch.cuda.synchronize(device)
     _check_converged(relres.cpu().numpy(), rtol, [f"#{i} (seed {s})" for i, s in enumerate(seeds)])
     return K, p, res, iters
 
 
-def solve_darcy_pressure(K, pixels_at_boundary=True, reverse_dy=True, domain_length=1., max_iter=MAX_ITER, rtol=RTOL, lib=None,
-                         return_iters=False):
-    """The reference's least-squares pressure for given permeability fields K ([B,P,P] or [P,P], fp64 on the device).
-    Returns (p shaped like K, res [B]) - and iters [B] with return_iters."""
+def solve_darcy_pressure(K, pixels_at_boundary=True, reverse_dy=True, domain_length=1., max_iter=None, rtol=RTOL, lib=None,
+                         return_iters=False, acc=2, iters_per_launch=None, resumable=False):
+    """The reference's least-squares pressure for given permeability fields K ([B,P,P] or [P,P], fp64 on the device) at
+    finite-difference order `acc`.  Returns (p shaped like K, res [B]) - and iters [B] with return_iters.  max_iter,
+    iters_per_launch, resumable: see generate_darcy_batch."""
     if not isinstance(K, torch.Tensor):
         raise PidmError("solve_darcy_pressure: K must be a torch tensor on the device")
     if lib is None and not K.is_cuda:
@@ -216,9 +290,11 @@ def solve_darcy_pressure(K, pixels_at_boundary=True, reverse_dy=True, domain_len
     if K.dim() != 3 or K.shape[1] != K.shape[2]:
         raise PidmError(f"solve_darcy_pressure: K of shape {tuple(shape)} is not [B,P,P] or [P,P]")
     B, P = K.shape[0], K.shape[1]
-    prob = DarcyProblem(P, pixels_at_boundary, reverse_dy, domain_length)
+    prob = DarcyProblem(P, pixels_at_boundary, reverse_dy, domain_length, acc)
+    max_iter = MAX_ITER_ACC[acc] if max_iter is None else max_iter
     Kin = K.to(torch.float64).reshape(B, P * P).contiguous()
-    _, p, res, iters, relres = _launch(lib, K.device, prob, K_in=Kin, B=B, max_iter=max_iter, rtol=rtol)
+    _, p, res, iters, relres = _launch(lib, K.device, prob, K_in=Kin, B=B, max_iter=max_iter, rtol=rtol,
+                                       iters_per_launch=iters_per_launch, resumable=resumable)
     if K.is_cuda:
         torch.cuda.synchronize(K.device)
     _check_converged(relres.cpu().numpy(), rtol, [f"#{i}" for i in range(B)])
@@ -240,11 +316,12 @@ def _unique_seeds(n, seed=None):
 
 
 def generate_darcy_dataset(n_samples, out_dir, seed=None, seeds=None, batch=256, pixels_per_dim=64, q=64, length_scale=0.1,
-                           pixels_at_boundary=True, reverse_dy=True, domain_length=1., max_iter=MAX_ITER, rtol=RTOL,
-                           cache_dir=None, device=None, lib=None, verbose=False):
+                           pixels_at_boundary=True, reverse_dy=True, domain_length=1., max_iter=None, rtol=RTOL,
+                           cache_dir=None, device=None, lib=None, verbose=False, acc=2, iters_per_launch=None, resumable=False):
     """Writes out_dir/{seeds,K_data,p_data,res_data}.csv exactly as the reference main() (no header, no index, one row per
     sample) plus kle_basis.npy (the scaled basis the seeds were expanded in: a seed fixes K only together with it).
-    `seeds` (explicit, must be distinct) or `seed` (draws n_samples distinct seeds reproducibly); neither: fresh ones."""
+    `seeds` (explicit, must be distinct) or `seed` (draws n_samples distinct seeds reproducibly); neither: fresh ones.
+    `acc`: the finite-difference order of the system the pressures solve (use the fd_acc the model will be trained with)."""
     import pandas as pd
     if seeds is None:
         seeds = _unique_seeds(n_samples, seed)
@@ -257,13 +334,14 @@ def generate_darcy_dataset(n_samples, out_dir, seed=None, seeds=None, batch=256,
     if batch < 1:
         raise PidmError("generate_darcy_dataset: batch must be >= 1")
     P = pixels_per_dim
-    DarcyProblem(P, pixels_at_boundary, reverse_dy, domain_length)     # argument checks before the eigendecomposition
+    DarcyProblem(P, pixels_at_boundary, reverse_dy, domain_length, acc)     # argument checks before the eigendecomposition
     basis = kle_basis(P, length_scale, q, pixels_at_boundary, cache_dir, domain_length)
     Ks, ps, rs = [], [], []
     t0 = time.time()
     for lo in range(0, n_samples, batch):
         K, p, res, iters = generate_darcy_batch(seeds[lo:lo + batch], P, q, length_scale, pixels_at_boundary, reverse_dy,
-                                                domain_length, basis=basis, max_iter=max_iter, rtol=rtol, device=device, lib=lib)
+                                                domain_length, basis=basis, max_iter=max_iter, rtol=rtol, device=device, lib=lib,
+                                                acc=acc, iters_per_launch=iters_per_launch, resumable=resumable)
         Ks.append(K.cpu().numpy())
         ps.append(p.cpu().numpy())
         rs.append(res.cpu().numpy())
@@ -284,15 +362,15 @@ def generate_sample(args):
     eigenpairs on the host, the least-squares solve on the engine."""
     (i, eigenvalues, eigenvectors, q, pixels_per_dim, shape, acc, d0, d1, f_s, int_cond, xmin_bd, xmax_bd, ymin_bd, ymax_bd,
      reverse_dy) = args
-    if acc != 2:
-        raise PidmError("the gfx950 solve implements acc=2 (model.yaml:13)")
+    if acc not in ACCS:
+        raise PidmError(f"the gfx950 solve implements acc in {ACCS}, not {acc!r}")
     unique_seed = os.getpid() * int(time.time() * 1000) % (2 ** 32)
     G, _ = KLE_expansion(eigenvalues, eigenvectors, q, pixels_per_dim ** 2, seed=unique_seed)
     K = np.exp(G.reshape(shape))
     P = pixels_per_dim
     pixels_at_boundary = np.shape(int_cond) == tuple(shape)      # create_int_cond: trapezoid weights [P,P], else a mean [P^2,1]
     p, res = solve_darcy_pressure(torch.from_numpy(K).to(_resolve(None, None)[0]), pixels_at_boundary=pixels_at_boundary,
-                                  reverse_dy=reverse_dy, domain_length=abs(d0) * ((P - 1) if pixels_at_boundary else P))
+                                  reverse_dy=reverse_dy, domain_length=abs(d0) * ((P - 1) if pixels_at_boundary else P), acc=acc)
     return K.flatten(), p.cpu().numpy().flatten(), float(res.cpu()[0]), unique_seed
 
 
@@ -307,14 +385,18 @@ def main(argv=None):
     ap.add_argument("--length-scale", type=float, default=DEFAULTS["length_scale"])
     ap.add_argument("--pixels-at-boundary", type=int, default=1)
     ap.add_argument("--reverse-dy", type=int, default=1)
-    ap.add_argument("--max-iter", type=int, default=MAX_ITER)
+    ap.add_argument("--acc", type=int, default=2, choices=ACCS, help="finite-difference order of the system (the model's fd_acc)")
+    ap.add_argument("--max-iter", type=int, default=None, help="default: MAX_ITER_ACC of the order")
+    ap.add_argument("--iters-per-launch", type=int, default=None,
+                    help="acc 4 / 6: CGLS iterations per kernel launch for a batch of one workgroup per compute unit")
     ap.add_argument("--rtol", type=float, default=RTOL)
     ap.add_argument("--cache-dir", default=None, help="where the KLE basis is cached (default: not cached)")
     a = ap.parse_args(argv)
     t0 = time.time()
     generate_darcy_dataset(a.n_samples, a.out, seed=a.seed, batch=a.batch, pixels_per_dim=a.pixels_per_dim, q=a.q,
                            length_scale=a.length_scale, pixels_at_boundary=bool(a.pixels_at_boundary),
-                           reverse_dy=bool(a.reverse_dy), max_iter=a.max_iter, rtol=a.rtol, cache_dir=a.cache_dir, verbose=True)
+                           reverse_dy=bool(a.reverse_dy), max_iter=a.max_iter, rtol=a.rtol, cache_dir=a.cache_dir, verbose=True,
+                           acc=a.acc, iters_per_launch=a.iters_per_launch)
     print(f"Data generation finished: {a.n_samples} samples in {time.time() - t0:.1f} s -> {a.out}")
 
 

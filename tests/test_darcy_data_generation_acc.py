@@ -1,0 +1,270 @@
+"""Darcy training-data generation at finite-difference orders 4 and 6 (csrc/k_darcy_gen_acc.hip, the `acc` keyword of
+physicsinformeddiffusionmodels_amd/darcy_data_generation.py) against a dense float64 least-squares oracle built from
+grad_utils.fd_coefficients, the reference generator's golden samples (g28), the second-order kernel, the launch-split protocol and
+the engine's own training residual at the same order."""
+import functools
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from physicsinformeddiffusionmodels_amd import darcy_data_generation as D
+from physicsinformeddiffusionmodels_amd import grad_utils as G
+from physicsinformeddiffusionmodels_amd._lib import PidmError, ptr, stream_ptr
+
+# the project's figure for this solve (tests/test_darcy_data_generation.py).  A NumPy CGLS with the kernel's algorithm (column
+# scaling, rtol 1e-12, deflation) stays at or below 3.4e-9 on p and 1.4e-9 on the residual for every case here.
+TOL = 1e-6
+CASES = [(True, True), (True, False), (False, True), (False, False)]
+
+
+def _d(P, h, order, acc):
+    """Dense 1-D operator by findiff's class rule: rows i < acc/2 forward, rows i > P-1-acc/2 backward, the others central."""
+    M, mio = np.zeros((P, P)), acc // 2
+    for i in range(P):
+        cls = "L" if i < mio else ("H" if i > P - 1 - mio else "C")
+        for o, w in G.fd_coefficients(order, acc, cls).items():
+            M[i, i + o] = w
+    return M / h ** order
+
+
+@functools.lru_cache(maxsize=None)
+def _system(P, pab, rev, acc, seed):
+    """(K, A_bc_int, b) of the reference system (src/darcy_data_generation.py:135-163, same row order) at order acc."""
+    K = _field(P, pab, seed)
+    pr = D.DarcyProblem(P, pab, rev, acc=acc)
+    eye = np.eye(P)
+    A0, A00 = np.kron(_d(P, pr.d0, 1, acc), eye), np.kron(_d(P, pr.d0, 2, acc), eye)
+    A1, A11 = np.kron(eye, _d(P, pr.d1, 1, acc)), np.kron(eye, _d(P, pr.d1, 2, acc))
+    k = K.reshape(-1)
+    k0, k1 = A0 @ k, A1 @ k
+    A = -k[:, None] * A00 - k0[:, None] * A0 - k[:, None] * A11 - k1[:, None] * A1
+    xmin, xmax, ymin, ymax = D.create_boundary_idcs((P, P))
+    s = 1. if rev else -1.
+    Abi = np.concatenate([A, -A0[xmin], A0[xmax], s * A1[ymin], -s * A1[ymax], pr.int_w.reshape(1, -1)])
+    b = np.concatenate([pr.f_s, np.zeros(4 * P + 1)])
+    return K, Abi, b
+
+
+@functools.lru_cache(maxsize=None)
+def dense_lstsq(P, pab, rev, acc, seed):
+    """(K, p, mean |row residual|) by lstsq; computed once per case and shared (callers do not modify the arrays)."""
+    K, Abi, b = _system(P, pab, rev, acc, seed)
+    p = np.linalg.lstsq(Abi, b, rcond=None)[0]
+    return K, p, np.abs(Abi @ p - b).mean()
+
+
+@functools.lru_cache(maxsize=None)
+def _basis(P, pab):
+    return D.kle_basis(P, 0.1, min(64, P * P), pab)
+
+
+def _field(P, pab, seed):
+    basis = _basis(P, pab)
+    return np.exp(basis.T @ D.z_of_seed(seed, basis.shape[0])).reshape(P, P)
+
+
+def _emu_or_gpu(backend):
+    L, dev = backend
+    return (L if dev.type == "cpu" else None), dev
+
+
+def _dense_case(lib, dev, P, pab, rev, acc):
+    seeds = (11 + P, 977)
+    ref = [dense_lstsq(P, pab, rev, acc, s) for s in seeds]
+    K = np.stack([r[0] for r in ref])
+    p, res, iters = D.solve_darcy_pressure(torch.from_numpy(K).to(dev), pab, rev, lib=lib, acc=acc, return_iters=True)
+    p, res = p.cpu().numpy(), res.cpu().numpy()
+    for s, (_, pref, rref) in enumerate(ref):
+        ep, er = np.abs(p[s].reshape(-1) - pref).max() / np.abs(pref).max(), abs(res[s] - rref) / rref
+        print(f"acc {acc} P {P} pab {pab} rev {rev} seed {seeds[s]}: iters {int(iters[s])} err p {ep:.3e} err res {er:.3e}")
+        assert ep <= TOL
+        assert er <= TOL
+
+
+# ---- 1. dense oracle ------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("acc,P", [(4, 8), (4, 16), (6, 10)])   # P = 8 at acc 4, P = 10 at acc 6: edge classes meet the central band
+@pytest.mark.parametrize("pab,rev", CASES)
+def test_solve_matches_dense_lstsq(backend, acc, P, pab, rev):
+    _dense_case(*_emu_or_gpu(backend), P, pab, rev, acc)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pab,rev", CASES)
+def test_solve_matches_dense_lstsq_acc6_p16(pab, rev):
+    _dense_case(None, torch.device("cuda:0"), 16, pab, rev, 6)
+
+
+@pytest.mark.gpu
+def test_solve_matches_dense_lstsq_acc4_p32():
+    _dense_case(None, torch.device("cuda:0"), 32, True, True, 4)
+
+
+# ---- 2. the reference generator's samples -----------------------------------------------------------------------------------------
+
+def _golden_solve(golden_dir, acc, lib, dev):
+    g = np.load(os.path.join(golden_dir, "g28_darcy_data_acc.npz"))
+    P = 16
+    K = np.stack([g[f"P{P}_acc{acc}_s{s}_K"].reshape(P, P) for s in range(2)])
+    p, res = D.solve_darcy_pressure(torch.from_numpy(K).to(dev), lib=lib, acc=acc)
+    for s in range(2):
+        pref, rref = g[f"P{P}_acc{acc}_s{s}_p"], float(g[f"P{P}_acc{acc}_s{s}_res"])
+        assert np.abs(p[s].cpu().numpy().reshape(-1) - pref).max() <= TOL * np.abs(pref).max()
+        assert abs(float(res[s]) - rref) <= TOL * rref
+
+
+def test_golden_solve_acc4(backend, golden_dir):
+    lib, dev = _emu_or_gpu(backend)
+    _golden_solve(golden_dir, 4, lib, dev)
+
+
+@pytest.mark.gpu
+def test_golden_solve_acc6(golden_dir):
+    _golden_solve(golden_dir, 6, None, torch.device("cuda:0"))
+
+
+# ---- 3. launch split ----------------------------------------------------------------------------------------------------------------
+
+def test_split_invariance(backend):
+    """A solve cut into launches of 7 or 100 iterations is bit-identical to the same solve in one launch; the sample that finishes
+    many launches before its neighbour (seed 27: ~1.6 k iterations, seed 977: ~2.0 k) is left untouched by the later ones."""
+    lib, dev = _emu_or_gpu(backend)
+    P, acc = 10, 6
+    K = torch.from_numpy(np.stack([_field(P, True, 977), _field(P, True, 27)])).to(dev)
+    runs = [D.solve_darcy_pressure(K, lib=lib, acc=acc, iters_per_launch=n, return_iters=True) for n in (10 ** 9, 100, 7)]
+    p1, r1, it1 = runs[0]
+    for n in (100, 7):
+        assert (int(it1[0]) - 1) // n != (int(it1[1]) - 1) // n        # they do finish in different launches
+    for p, r, it in runs[1:]:
+        assert torch.equal(it, it1)
+        assert torch.equal(p, p1)
+        assert torch.equal(r, r1)
+
+
+# ---- 4. second order through the new entry --------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("P", [8, 16])
+def test_resumable_acc2_matches_second_order_kernel(backend, P):
+    lib, dev = _emu_or_gpu(backend)
+    K = torch.from_numpy(np.stack([_field(P, True, 11 + P), _field(P, True, 977)])).to(dev)
+    pref, rref = D.solve_darcy_pressure(K, lib=lib)
+    p, r = D.solve_darcy_pressure(K, lib=lib, acc=2, resumable=True, iters_per_launch=300)
+    for s in range(2):
+        assert float((p[s] - pref[s]).abs().max()) <= TOL * float(pref[s].abs().max())
+        assert abs(float(r[s]) - float(rref[s])) <= TOL * float(rref[s])
+
+
+# ---- 5. batch invariance ----------------------------------------------------------------------------------------------------------------
+
+def test_batch_invariance(backend):
+    lib, dev = _emu_or_gpu(backend)
+    P = 10
+    basis = _basis(P, True)
+    seeds = list(range(100, 113))
+    Kb, pb, rb, _ = D.generate_darcy_batch(seeds, P, basis=basis, device=dev, lib=lib, acc=4)
+    K1, p1, r1, _ = D.generate_darcy_batch([seeds[7]], P, basis=basis, device=dev, lib=lib, acc=4)
+    assert torch.equal(Kb[7], K1[0]) and torch.equal(pb[7], p1[0]) and torch.equal(rb[7], r1[0])
+
+
+# ---- 6. consistency with the training residual ----------------------------------------------------------------------------------------------
+
+@pytest.mark.gpu
+def test_consistent_with_training_residual():
+    """Why the generator takes the order: data solved at order a has, under ResidualsDarcy(fd_acc=a), the mean |row residual| the
+    generator reports; second-order data under the fourth-order rows carries a residual more than ten times larger (dense float64:
+    x 128 for seed 977, x 27 for seed 27)."""
+    from physicsinformeddiffusionmodels_amd.residuals_darcy import ResidualsDarcy
+    P, dev = 16, torch.device("cuda:0")
+    rows = P * P + 4 * P + 1
+    K = torch.from_numpy(np.stack([_field(P, True, 977), _field(P, True, 27)])).to(dev)
+
+    def mean_abs(rd, p):
+        x = torch.stack([p, K], dim=1).float()
+        return (rd.residual_of(x).double().abs().sum(dim=(1, 2)) / rows).cpu().numpy()
+
+    own = {}
+    for a in (4, 6):
+        rd = ResidualsDarcy(model=None, fd_acc=a, pixels_per_dim=P, pixels_at_boundary=True, reverse_d1=True, device="cuda:0")
+        p, res = D.solve_darcy_pressure(K, acc=a)
+        own[a] = mean_abs(rd, p)
+        print(f"acc {a}: training residual {own[a]}, generator {res.cpu().numpy()}")
+        # fp32 bound of tests/test_darcy_data_generation.py::test_dataset_round_trip_into_training (at P = 16 the stencil terms
+        # are 16 times smaller than there)
+        np.testing.assert_allclose(own[a], res.cpu().numpy(), rtol=5e-3)
+        if a == 4:
+            p2, _ = D.solve_darcy_pressure(K)
+            cross = mean_abs(rd, p2)
+            print(f"second-order data under fd_acc=4: {cross}, ratio {cross / own[4]}")
+            assert (cross >= 10 * own[4]).all()
+
+
+# ---- 7. errors ----------------------------------------------------------------------------------------------------------------------------
+
+def test_errors(backend):
+    lib, dev = _emu_or_gpu(backend)
+    one = lambda P: torch.ones(1, P, P, dtype=torch.float64, device=dev)   # noqa: E731
+    for bad in (3, 8):
+        with pytest.raises(PidmError, match=f"acc={bad}"):
+            D.solve_darcy_pressure(one(16), lib=lib, acc=bad)
+        with pytest.raises(PidmError, match=f"acc={bad}"):
+            D.generate_darcy_batch([1], 16, basis=np.zeros((4, 256)), device=dev, lib=lib, acc=bad)
+    for P in (8, 9):
+        with pytest.raises(PidmError, match=r"outside \[10, 64\] at acc=6"):
+            D.solve_darcy_pressure(one(P), lib=lib, acc=6)
+    with pytest.raises(PidmError, match="outside"):
+        D.solve_darcy_pressure(one(65), lib=lib, acc=4)
+    P = 10
+    with pytest.raises(PidmError, match=r"did not converge.*#0 \(seed 1\).*#1 \(seed 2\)"):
+        D.generate_darcy_batch([1, 2], P, basis=_basis(P, True), device=dev, lib=lib, acc=4, max_iter=3)
+    with pytest.raises(PidmError, match="iters_per_launch"):
+        D.solve_darcy_pressure(one(P), lib=lib, acc=4, iters_per_launch=0)
+    # the native entry point itself rejects what the Python layer would have caught
+    L = lib or __import__("physicsinformeddiffusionmodels_amd._lib", fromlist=["get_lib"]).get_lib()
+    f = torch.zeros(P * P, dtype=torch.float64, device=dev)
+    Kin = torch.ones(1, P * P, dtype=torch.float64, device=dev)
+    out = torch.zeros(1, P * P, dtype=torch.float64, device=dev)
+    done = torch.zeros(1, dtype=torch.int32, device=dev)
+    state = torch.zeros(L.pidm_darcy_gen_acc_state_bytes(P, 1) // 8, dtype=torch.float64, device=dev)
+    assert L.pidm_darcy_gen_acc_state_bytes(P, 1) == (3 * P * P + 4 * P + 3) * 8
+
+    def call(acc=4, P_=P, st=state, n=10):
+        return L.pidm_darcy_gen_acc(None, None, 0, ptr(Kin), P_, acc, 0.1, 0.1, 1.0, ptr(f), ptr(f), 10, 1e-10, n, 1, ptr(st), None,
+                                    ptr(out), None, None, None, ptr(done), 1, stream_ptr(dev))
+    assert call(acc=5) != 0 and b"acc=5" in L.pidm_last_error()
+    assert call(st=None) != 0 and b"state" in L.pidm_last_error()
+    assert call(n=0) != 0 and b"iters_this_launch" in L.pidm_last_error()
+    assert call(acc=6, P_=9) != 0 and b"acc=6" in L.pidm_last_error()
+    assert L.pidm_darcy_gen_acc_lds_bytes(64, 6) <= 160 * 1024 and L.pidm_darcy_gen_acc_lds_bytes(64, 5) == 0
+
+
+def test_generate_sample_rejects_unknown_order():
+    args = (0, np.ones(4), np.zeros((256, 4)), 4, 16, (16, 16), 8, 1 / 15, -1 / 15, np.zeros(256), np.zeros((16, 16)),
+            None, None, None, None, True)
+    with pytest.raises(PidmError, match="acc"):
+        D.generate_sample(args)
+
+
+# ---- 8. the dataset files ------------------------------------------------------------------------------------------------------------------
+
+def test_dataset_csv_round_trip(backend, tmp_path):
+    import pandas as pd
+    lib, dev = _emu_or_gpu(backend)
+    P, n = 16, 3
+    out = str(tmp_path / "darcy4")
+    seeds = D.generate_darcy_dataset(n, out, seed=3, batch=3, pixels_per_dim=P, acc=4, device=dev, lib=lib)
+    assert seeds == D._unique_seeds(n, 3)
+    arrs = {}
+    for name, cols in (("seeds", 1), ("K_data", P * P), ("p_data", P * P), ("res_data", 1)):
+        arrs[name] = pd.read_csv(os.path.join(out, name + ".csv"), header=None).to_numpy()
+        assert arrs[name].shape == (n, cols), name
+    assert arrs["seeds"][:, 0].tolist() == seeds
+    basis = np.load(os.path.join(out, "kle_basis.npy"))
+    assert basis.shape == (64, P * P)
+    for i, s in enumerate(seeds):
+        np.testing.assert_allclose(arrs["K_data"][i], np.exp(basis.T @ D.z_of_seed(s, 64)), rtol=1e-12)
+    # the pressures are those of the fourth-order system of the same fields
+    _, pref, rref = dense_lstsq(P, True, True, 4, seeds[0])
+    assert np.abs(arrs["p_data"][0] - pref).max() <= TOL * np.abs(pref).max()
+    assert abs(arrs["res_data"][0, 0] - rref) <= TOL * rref

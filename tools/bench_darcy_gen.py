@@ -1,8 +1,10 @@
 """Throughput of the Darcy data generator (csrc/k_darcy_gen.hip) on the MI355X: samples/s and CGLS iterations per sample
 (min / median / max) at P = 64 for batches of 256 and 1024, and at P = 32.  The KLE basis (host eigh) is computed once per P
-and not timed.  Results go to stdout; DESIGN.md / profiles/ keep the recorded numbers.
+and not timed.  --acc 4 / 6 (csrc/k_darcy_gen_acc.hip) and --resumable (acc 2 through the same entry) also report the number of
+launches and the longest single launch (launch + read-back of the done flags).  Results go to stdout; DESIGN.md / profiles/ keep the
+recorded numbers.
 
-    python tools/bench_darcy_gen.py [--cases 64:256,64:1024,32:256]
+    python tools/bench_darcy_gen.py [--cases 64:256,64:1024,32:256] [--acc 4] [--iters-per-launch N] [--resumable]
 """
 import argparse
 import os
@@ -19,7 +21,12 @@ from physicsinformeddiffusionmodels_amd import darcy_data_generation as D  # noq
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="64:256,64:1024,32:256")
+    ap.add_argument("--acc", type=int, default=2, choices=D.ACCS)
+    ap.add_argument("--iters-per-launch", type=int, default=None)
+    ap.add_argument("--resumable", action="store_true", help="acc 2 through the resumable entry")
+    ap.add_argument("--max-iter", type=int, default=None)
     a = ap.parse_args()
+    kw = dict(acc=a.acc, iters_per_launch=a.iters_per_launch, resumable=a.resumable, max_iter=a.max_iter)
     dev = torch.device("cuda:0")
     bases = {}
     for case in a.cases.split(","):
@@ -27,14 +34,19 @@ def main():
         if P not in bases:
             bases[P] = D.kle_basis(P, 0.1, 64, True)
         seeds = list(range(1000, 1000 + B))
-        D.generate_darcy_batch(seeds[:8], P, basis=bases[P], device=dev)          # warm-up (module load, LDS attribute)
+        D.generate_darcy_batch(seeds[:8], P, basis=bases[P], device=dev, **dict(kw, max_iter=10), rtol=1.)   # warm-up (module
+        #                                                                    load, LDS attribute); rtol 1: converged at once
         torch.cuda.synchronize()
         t = time.perf_counter()
-        K, p, res, iters = D.generate_darcy_batch(seeds, P, basis=bases[P], device=dev)
+        st = {}
+        K, p, res, iters = D.generate_darcy_batch(seeds, P, basis=bases[P], device=dev, stats=st, **kw)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t
         it = iters.cpu().numpy()
-        print(f"P={P} B={B}: {dt:.3f} s, {B / dt:.1f} samples/s, iterations min {it.min()} median {int(np.median(it))} "
+        entry = "pidm_darcy_gen" if st["longest_launch_s"] is None else (
+            f"pidm_darcy_gen_acc, {st['launches']} launches of <= {st['iters_per_launch']} iterations, longest "
+            f"{st['longest_launch_s']:.3f} s")
+        print(f"P={P} B={B} acc={a.acc} ({entry}): {dt:.3f} s, {B / dt:.1f} samples/s, iterations min {it.min()} median {int(np.median(it))} "
               f"max {it.max()}, {dt / B * 1e3:.2f} ms/sample, {dt / it.max() * 1e6:.2f} us per iteration of the batch, "
               f"res {float(res.mean()):.3e}", flush=True)
 
