@@ -250,8 +250,24 @@ int pidm_darcy_gen_acc(const double* basis, const double* z, int q, const double
                        double bc_sign, const double* int_w, const double* f_s, int max_iter, double rtol, int iters_this_launch,
                        int first_launch, void* state, double* K_out, double* p_out, double* res_mean, int32_t* iters,
                        double* relres, int32_t* done, int B, void* stream);
+/*   pidm_darcy_gen_periodic: the same system under periodic boundary conditions - src/darcy_data_generation.py:129-163 with every
+ *                   FinDiff(..., acc=acc) replaced by its central stencil of order acc in {2, 4, 6} on wrapped indices (tap i + o
+ *                   reads point (i + o) mod P on both axes), the operators of ResidualsDarcy(bcs='periodic'); the reference's
+ *                   generator has no such mode (main.py's bcs = 'periodic' reaches training only).  K_0 and K_1 come from the same
+ *                   operators.  The four boundary row sets stay: -(D0 p) on row 0, +(D0 p) on row P-1, bc_sign (D1 p) on column 0,
+ *                   -bc_sign (D1 p) on column P-1, with the wrapped D0 / D1.  Arguments, launch protocol, `state` layout (size:
+ *                   pidm_darcy_gen_acc_state_bytes(P, B)) and outputs as pidm_darcy_gen_acc.  Limits: 8 <= P <= 64 at every order
+ *                   (the wrapped stencil of order 6 spans 7 points); anything else, a null state or iters_this_launch < 1 is an
+ *                   error.
+ *   pidm_darcy_gen_periodic_lds_bytes: LDS per workgroup (four P^2 fields, 4P boundary residuals, the (acc+2) x 2 coefficient
+ *                   table, the reduction slots).  0 for an order other than 2, 4, 6. */
+size_t pidm_darcy_gen_periodic_lds_bytes(int P, int acc);
+int pidm_darcy_gen_periodic(const double* basis, const double* z, int q, const double* K_in, int P, int acc, double d0, double d1,
+                            double bc_sign, const double* int_w, const double* f_s, int max_iter, double rtol,
+                            int iters_this_launch, int first_launch, void* state, double* K_out, double* p_out, double* res_mean,
+                            int32_t* iters, double* relres, int32_t* done, int B, void* stream);
 
-/* Mechanics training-data generation      replaces nothing in the reference: it never generated its topology-optimisation samples
+/* Mechanics training-data generation     replaces nothing in the reference: it never generated its topology-optimisation samples
  * (they were downloaded); these entries supply the data main.py:90-101 expects (one [65,65,10] .npy per sample), DESIGN section 4b
  *   pidm_simp_step: ONE iteration of SIMP compliance minimisation for B samples, one workgroup per sample, all in fp64, stateless:
  *                   (x [B, nel*nel] densities, u [B, ndof] warm start) -> (x_new, u_out = the solved displacements).  Per sample:

@@ -88,6 +88,9 @@ class PidmLib:
         self._sig("pidm_darcy_gen_acc_lds_bytes", [i, i], sz)
         self._sig("pidm_darcy_gen_acc", [vp, vp, i, vp, i, i, C.c_double, C.c_double, C.c_double, vp, vp, i, C.c_double, i, i, vp,
                                          vp, vp, vp, vp, vp, vp, i, vp])
+        self._sig("pidm_darcy_gen_periodic_lds_bytes", [i, i], sz)
+        self._sig("pidm_darcy_gen_periodic", [vp, vp, i, vp, i, i, C.c_double, C.c_double, C.c_double, vp, vp, i, C.c_double, i, i,
+                                              vp, vp, vp, vp, vp, vp, vp, i, vp])
         d = C.c_double
         self._sig("pidm_simp_ws_bytes", [i, i], sz)
         self._sig("pidm_simp_step", [vp, vp, vp, vp, vp, vp, i, vp, vp, i, d, d, d, d, i, i, d, vp, vp, vp, vp, vp, vp, vp, i, vp])

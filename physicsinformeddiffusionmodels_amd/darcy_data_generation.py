@@ -6,11 +6,14 @@ with `scipy.linalg.lstsq` (7.2 s per 64 x 64 sample on one CPU core).  Here the 
 and the solve runs in `csrc/k_darcy_gen.hip`: one workgroup per sample, KLE synthesis and matrix-free column-scaled CGLS in
 fp64 ("Darcy data generation").  `acc` (the reference's finite-difference order, 2 / 4 / 6) selects the operators: 2 is
 that kernel; 4 and 6 run in `csrc/k_darcy_gen_acc.hip`, in launches of a bounded number of iterations that carry the CGLS state
-between them.  Host-side pieces are the grid, the eigendecomposition of the covariance (the
-reference's exact full `eigh`, cached) and the CSV writing.  There is no CPU fallback for the solve.
+between them.  `bcs='periodic'` solves the system of `ResidualsDarcy(bcs='periodic')` instead - every operator central, on wrapped
+indices - in `csrc/k_darcy_gen_per.hip` (same launches), on permeability fields of a wrapped-distance covariance.  Host-side
+pieces are the grid, the eigendecomposition of the covariance (the reference's exact full `eigh`, cached) and the CSV writing.
+There is no CPU fallback for the solve.
 
     python -m physicsinformeddiffusionmodels_amd.darcy_data_generation --n-samples 10000 --out ./data/darcy/train
     python -m physicsinformeddiffusionmodels_amd.darcy_data_generation --n-samples 10000 --out ./data/darcy/train4 --acc 4
+    python -m physicsinformeddiffusionmodels_amd.darcy_data_generation --n-samples 10000 --out ./data/darcy/trainp --bcs periodic
 """
 from __future__ import annotations
 
@@ -29,6 +32,7 @@ DEFAULTS = dict(pixels_per_dim=64, pixels_at_boundary=True, domain_length=1., le
 RTOL = 1e-12          # ||S A^T r|| / ||S A^T b|| at which a sample counts as solved (tests/test_darcy_data_generation.py)
 MAX_ITER = 200000     # P = 64 takes ~40-50k iterations
 ACCS = (2, 4, 6)
+BCS = ('none', 'periodic')     # the reference's main.py: bcs = 'none' # 'none', 'periodic'
 # max_iter=None: about twice the largest count measured at P = 64 (profiles/darcy_gen_bench_acc.txt)
 MAX_ITER_ACC = {2: MAX_ITER, 4: 1000000, 6: 4000000}     # measured maxima at P = 64, batch 256: 494 k (acc 4), 2.04 M (acc 6)
 # iterations per launch of the resumable entry for a batch of at most one workgroup per compute unit: a launch at P = 64, acc 6,
@@ -62,6 +66,14 @@ def create_f_s(x, y, w=0.125, r=10.):
 def complete_covariance_matrix(grid, l):
     dx = grid[:, None, 0] - grid[None, :, 0]
     dy = grid[:, None, 1] - grid[None, :, 1]
+    return np.exp(-np.sqrt(dx ** 2 + dy ** 2) / l)
+
+
+def periodic_covariance_matrix(grid, l, period):
+    """complete_covariance_matrix with each axis distance taken around the ring: min(|d|, period - |d|)."""
+    dx = np.abs(grid[:, None, 0] - grid[None, :, 0])
+    dy = np.abs(grid[:, None, 1] - grid[None, :, 1])
+    dx, dy = np.minimum(dx, period - dx), np.minimum(dy, period - dy)
     return np.exp(-np.sqrt(dx ** 2 + dy ** 2) / l)
 
 
@@ -110,23 +122,34 @@ def z_of_seed(seed, q):
 
 # ---- the engine --------------------------------------------------------------------------------------------------------------
 
-def min_pixels(acc):
+def min_pixels(acc, bcs='none'):
     """Smallest grid of order acc: rows below acc/2 use forward stencils, and the second-derivative one of row acc/2 - 1 reaches
-    column 3 acc/2 (9 at acc 6); 8 below that, as the second-order kernel."""
-    return max(8, 3 * acc // 2 + 1)
+    column 3 acc/2 (9 at acc 6); 8 below that, as the second-order kernel.  Periodic: 8 at every order (the widest wrapped stencil
+    spans 7 points)."""
+    return 8 if bcs == 'periodic' else max(8, 3 * acc // 2 + 1)
+
+
+def _check_bcs(bcs):
+    if bcs not in BCS:
+        raise PidmError(f"darcy data generation: bcs={bcs!r} is not one of {BCS}")
+    return bcs == 'periodic'
 
 
 class DarcyProblem:
     """Grid-dependent, sample-independent data of the reference system: spacings, boundary sign, f_s and integral weights."""
 
-    def __init__(self, P, pixels_at_boundary=True, reverse_dy=True, domain_length=1., acc=2):
+    def __init__(self, P, pixels_at_boundary=True, reverse_dy=True, domain_length=1., acc=2, bcs='none'):
         if acc not in ACCS:
             raise PidmError(f"darcy data generation: acc={acc!r} is not one of the orders {ACCS} the gfx950 solve implements")
-        pmin = min_pixels(acc)
+        self.periodic = _check_bcs(bcs)
+        pmin = min_pixels(acc, bcs)
         if not pmin <= P <= 64:
-            raise PidmError(f"darcy data generation: pixels_per_dim={P} outside [{pmin}, 64] at acc={acc} (a one-sided second "
-                            f"derivative of order {acc} spans {acc + 2} points; the solve keeps four fp64 P x P fields in LDS)")
+            why = ("the wrapped stencil of order 6 spans 7 points" if self.periodic else
+                   f"a one-sided second derivative of order {acc} spans {acc + 2} points")
+            raise PidmError(f"darcy data generation: pixels_per_dim={P} outside [{pmin}, 64] at acc={acc}, bcs={bcs!r} ({why}; the "
+                            f"solve keeps four fp64 P x P fields in LDS)")
         self.P, self.pixels_at_boundary, self.reverse_dy, self.acc = P, bool(pixels_at_boundary), bool(reverse_dy), acc
+        self.bcs = bcs
         self.d0 = domain_length / (P - 1) if pixels_at_boundary else domain_length / P
         self.d1 = -self.d0 if reverse_dy else self.d0
         # y-min row: +D1 p with reverse_dy, -D1 p without (y-max the opposite), src/darcy_data_generation.py:147-150
@@ -153,21 +176,31 @@ def _resolve(device, lib):
     return device, lib
 
 
-def _basis_file(P, l, q, pixels_at_boundary, domain_length):
-    return f"kle_basis_P{P}_l{l!r}_q{q}_b{int(bool(pixels_at_boundary))}_L{domain_length!r}.npy"
+def _basis_file(P, l, q, pixels_at_boundary, domain_length, periodic=False):
+    return (f"kle_basis_P{P}_l{l!r}_q{q}_b{int(bool(pixels_at_boundary))}_L{domain_length!r}" + ("_periodic" if periodic else "")
+            + ".npy")
 
 
-def kle_basis(P=64, l=0.1, q=64, pixels_at_boundary=True, cache_dir=None, domain_length=1.):
+def kle_basis(P=64, l=0.1, q=64, pixels_at_boundary=True, cache_dir=None, domain_length=1., bcs='none'):
     """[q, P*P] float64: row k = sqrt(lambda_k) phi_k, the reference's eigenpairs (full eigh of the P^2 x P^2 covariance,
     descending).  Cached as .npy under cache_dir, keyed by the arguments.  Degenerate eigenpairs make the rows inside a pair
-    depend on the LAPACK build; their span does not."""
+    depend on the LAPACK build; their span does not.  bcs='periodic': the covariance of the wrapped distance, period
+    P x grid spacing (the spacing of DarcyProblem), so the fields continue smoothly across the edges the wrapped stencils cross."""
+    periodic = _check_bcs(bcs)
     if q < 1 or q > P * P:
         raise PidmError(f"kle_basis: q={q} outside [1, P^2={P * P}]")
-    path = os.path.join(cache_dir, _basis_file(P, l, q, pixels_at_boundary, domain_length)) if cache_dir else None
+    path = os.path.join(cache_dir, _basis_file(P, l, q, pixels_at_boundary, domain_length, periodic)) if cache_dir else None
     if path and os.path.exists(path):
         return np.load(path)
     pts = uniform_points_pixelwise(P, domain_length, pixels_at_boundary)
-    lam, phi = compute_eigenpairs(complete_covariance_matrix(pts, l), q)
+    if periodic:
+        period = P * (domain_length / (P - 1) if pixels_at_boundary else domain_length / P)
+        lam, phi = compute_eigenpairs(periodic_covariance_matrix(pts, l, period), q)
+        if not (lam > 0).all():      # (the wrapped exponential kernel is not positive definite by construction)
+            raise PidmError(f"kle_basis: the wrapped covariance at P={P}, l={l!r} has a non-positive eigenvalue among its first "
+                            f"{q} ({lam.min():.3e}): lower q")
+    else:
+        lam, phi = compute_eigenpairs(complete_covariance_matrix(pts, l), q)
     basis = np.ascontiguousarray((np.sqrt(lam)[None, :] * phi).T)
     if path:
         os.makedirs(cache_dir, exist_ok=True)
@@ -183,7 +216,7 @@ def _check_converged(relres, rtol, labels):
 
 def _launch(lib, device, prob, *, basis=None, z=None, K_in=None, B, max_iter, rtol, iters_per_launch=None, resumable=False,
             stats=None):
-    if prob.acc != 2 or resumable:
+    if prob.acc != 2 or resumable or prob.periodic:
         return _launch_acc(lib, device, prob, basis=basis, z=z, K_in=K_in, B=B, max_iter=max_iter, rtol=rtol,
                            iters_per_launch=iters_per_launch, stats=stats)
     P = prob.P
@@ -203,10 +236,13 @@ def _launch(lib, device, prob, *, basis=None, z=None, K_in=None, B, max_iter, rt
 
 
 def _launch_acc(lib, device, prob, *, basis=None, z=None, K_in=None, B, max_iter, rtol, iters_per_launch=None, stats=None):
-    """The resumable entry (csrc/k_darcy_gen_acc.hip): launches of at most `iters_per_launch` iterations per sample until every
-    sample is done; the B done flags are read back after each launch.  A batch larger than the device's compute units runs its
-    workgroups one behind the other, so the budget of a launch is divided by ceil(B / compute units)."""
+    """The resumable entries (csrc/k_darcy_gen_acc.hip, or csrc/k_darcy_gen_per.hip for a periodic problem: same arguments, same
+    state): launches of at most `iters_per_launch` iterations per sample until every sample is done; the B done flags are read back
+    after each launch.  A batch larger than the device's compute units runs its workgroups one behind the other, so the budget of
+    a launch is divided by ceil(B / compute units)."""
     P = prob.P
+    name = "pidm_darcy_gen_periodic" if prob.periodic else "pidm_darcy_gen_acc"
+    entry = getattr(lib, name)
     f_s, int_w = prob.on(device)
     if iters_per_launch is None:
         iters_per_launch = ITERS_PER_LAUNCH
@@ -229,16 +265,16 @@ def _launch_acc(lib, device, prob, *, basis=None, z=None, K_in=None, B, max_iter
     most = int(max_iter) // iters_per_launch + 2         # every launch advances every unfinished sample by iters_per_launch
     while True:
         t0 = time.perf_counter()
-        lib.check(lib.pidm_darcy_gen_acc(ptr(basis), ptr(z), q, ptr(K_in), P, prob.acc, prob.d0, prob.d1, prob.bc_sign, ptr(int_w),
-                                         ptr(f_s), int(max_iter), float(rtol), iters_per_launch, first, ptr(state), ptr(K), ptr(p),
-                                         ptr(res), ptr(iters), ptr(relres), ptr(done), B, stream_ptr(device)), "pidm_darcy_gen_acc")
+        lib.check(entry(ptr(basis), ptr(z), q, ptr(K_in), P, prob.acc, prob.d0, prob.d1, prob.bc_sign, ptr(int_w), ptr(f_s),
+                        int(max_iter), float(rtol), iters_per_launch, first, ptr(state), ptr(K), ptr(p), ptr(res), ptr(iters),
+                        ptr(relres), ptr(done), B, stream_ptr(device)), name)
         finished = bool(done.cpu().all())                # (a few hundred bytes; also waits for the launch)
         longest = max(longest, time.perf_counter() - t0)
         launches, first = launches + 1, 0
         if finished:
             break
         if launches >= most:
-            raise PidmError(f"pidm_darcy_gen_acc: samples unfinished after {launches} launches of {iters_per_launch} iterations "
+            raise PidmError(f"{name}: samples unfinished after {launches} launches of {iters_per_launch} iterations "
                             f"(max_iter={max_iter})")
     if stats is not None:
         stats.update(launches=launches, longest_launch_s=longest, iters_per_launch=iters_per_launch)
@@ -247,19 +283,20 @@ def _launch_acc(lib, device, prob, *, basis=None, z=None, K_in=None, B, max_iter
 
 def generate_darcy_batch(seeds, pixels_per_dim=64, q=64, length_scale=0.1, pixels_at_boundary=True, reverse_dy=True,
                          domain_length=1., basis=None, max_iter=None, rtol=RTOL, cache_dir=None, device=None, lib=None, acc=2,
-                         iters_per_launch=None, resumable=False, stats=None):
+                         iters_per_launch=None, resumable=False, stats=None, bcs='none'):
     """Samples for the given seeds: K = exp(KLE(z(seed))) and the reference's least-squares pressure p at finite-difference order
     `acc` (2, 4 or 6).  Returns (K [B,P*P], p [B,P*P], res [B], iters [B]) on the device, fp64 (res = mean |row residual| over all
     P^2+4P+1 rows).  `basis` ([q, P*P], see kle_basis) overrides the eigendecomposition.  max_iter=None: MAX_ITER_ACC[acc].
     acc 4 and 6 (and acc 2 with resumable=True) run in launches of at most `iters_per_launch` iterations (None: ITERS_PER_LAUNCH,
-    scaled to the batch); `stats` (a dict) receives the number of launches and the longest one."""
+    scaled to the batch); `stats` (a dict) receives the number of launches and the longest one.  bcs='periodic': the periodic system
+    (wrapped central operators, always in such launches) on fields of the periodic kle_basis."""
     device, lib = _resolve(device, lib)
     P = pixels_per_dim
-    prob = DarcyProblem(P, pixels_at_boundary, reverse_dy, domain_length, acc)
+    prob = DarcyProblem(P, pixels_at_boundary, reverse_dy, domain_length, acc, bcs)
     max_iter = MAX_ITER_ACC[acc] if max_iter is None else max_iter
     seeds = [int(s) for s in seeds]
     if basis is None:
-        basis = kle_basis(P, length_scale, q, pixels_at_boundary, cache_dir, domain_length)
+        basis = kle_basis(P, length_scale, q, pixels_at_boundary, cache_dir, domain_length, bcs)
     basis = np.ascontiguousarray(basis, dtype=np.float64)
     if basis.ndim != 2 or basis.shape[1] != P * P or not 1 <= basis.shape[0] <= P * P:
         raise PidmError(f"KLE basis of shape {basis.shape} does not fit q <= P^2 = {P * P} modes of {P} x {P}")
@@ -275,10 +312,10 @@ def generate_darcy_batch(seeds, pixels_per_dim=64, q=64, length_scale=0.1, pixel
 
 
 def solve_darcy_pressure(K, pixels_at_boundary=True, reverse_dy=True, domain_length=1., max_iter=None, rtol=RTOL, lib=None,
-                         return_iters=False, acc=2, iters_per_launch=None, resumable=False):
+                         return_iters=False, acc=2, iters_per_launch=None, resumable=False, bcs='none'):
     """The reference's least-squares pressure for given permeability fields K ([B,P,P] or [P,P], fp64 on the device) at
     finite-difference order `acc`.  Returns (p shaped like K, res [B]) - and iters [B] with return_iters.  max_iter,
-    iters_per_launch, resumable: see generate_darcy_batch."""
+    iters_per_launch, resumable, bcs: see generate_darcy_batch."""
     if not isinstance(K, torch.Tensor):
         raise PidmError("solve_darcy_pressure: K must be a torch tensor on the device")
     if lib is None and not K.is_cuda:
@@ -290,7 +327,7 @@ def solve_darcy_pressure(K, pixels_at_boundary=True, reverse_dy=True, domain_len
     if K.dim() != 3 or K.shape[1] != K.shape[2]:
         raise PidmError(f"solve_darcy_pressure: K of shape {tuple(shape)} is not [B,P,P] or [P,P]")
     B, P = K.shape[0], K.shape[1]
-    prob = DarcyProblem(P, pixels_at_boundary, reverse_dy, domain_length, acc)
+    prob = DarcyProblem(P, pixels_at_boundary, reverse_dy, domain_length, acc, bcs)
     max_iter = MAX_ITER_ACC[acc] if max_iter is None else max_iter
     Kin = K.to(torch.float64).reshape(B, P * P).contiguous()
     _, p, res, iters, relres = _launch(lib, K.device, prob, K_in=Kin, B=B, max_iter=max_iter, rtol=rtol,
@@ -317,11 +354,13 @@ def _unique_seeds(n, seed=None):
 
 def generate_darcy_dataset(n_samples, out_dir, seed=None, seeds=None, batch=256, pixels_per_dim=64, q=64, length_scale=0.1,
                            pixels_at_boundary=True, reverse_dy=True, domain_length=1., max_iter=None, rtol=RTOL,
-                           cache_dir=None, device=None, lib=None, verbose=False, acc=2, iters_per_launch=None, resumable=False):
+                           cache_dir=None, device=None, lib=None, verbose=False, acc=2, iters_per_launch=None, resumable=False,
+                           bcs='none'):
     """Writes out_dir/{seeds,K_data,p_data,res_data}.csv exactly as the reference main() (no header, no index, one row per
     sample) plus kle_basis.npy (the scaled basis the seeds were expanded in: a seed fixes K only together with it).
     `seeds` (explicit, must be distinct) or `seed` (draws n_samples distinct seeds reproducibly); neither: fresh ones.
-    `acc`: the finite-difference order of the system the pressures solve (use the fd_acc the model will be trained with)."""
+    `acc`: the finite-difference order of the system the pressures solve (use the fd_acc the model will be trained with);
+    `bcs`: 'none' or 'periodic', likewise the bcs of the training residual."""
     import pandas as pd
     if seeds is None:
         seeds = _unique_seeds(n_samples, seed)
@@ -334,14 +373,14 @@ def generate_darcy_dataset(n_samples, out_dir, seed=None, seeds=None, batch=256,
     if batch < 1:
         raise PidmError("generate_darcy_dataset: batch must be >= 1")
     P = pixels_per_dim
-    DarcyProblem(P, pixels_at_boundary, reverse_dy, domain_length, acc)     # argument checks before the eigendecomposition
-    basis = kle_basis(P, length_scale, q, pixels_at_boundary, cache_dir, domain_length)
+    DarcyProblem(P, pixels_at_boundary, reverse_dy, domain_length, acc, bcs)     # argument checks before the eigendecomposition
+    basis = kle_basis(P, length_scale, q, pixels_at_boundary, cache_dir, domain_length, bcs)
     Ks, ps, rs = [], [], []
     t0 = time.time()
     for lo in range(0, n_samples, batch):
         K, p, res, iters = generate_darcy_batch(seeds[lo:lo + batch], P, q, length_scale, pixels_at_boundary, reverse_dy,
                                                 domain_length, basis=basis, max_iter=max_iter, rtol=rtol, device=device, lib=lib,
-                                                acc=acc, iters_per_launch=iters_per_launch, resumable=resumable)
+                                                acc=acc, iters_per_launch=iters_per_launch, resumable=resumable, bcs=bcs)
         Ks.append(K.cpu().numpy())
         ps.append(p.cpu().numpy())
         rs.append(res.cpu().numpy())
@@ -359,7 +398,7 @@ def generate_darcy_dataset(n_samples, out_dir, seed=None, seeds=None, batch=256,
 
 def generate_sample(args):
     """The reference's per-sample worker: same argument tuple, same (K, p, mean |residual|, seed) result; K from the given
-    eigenpairs on the host, the least-squares solve on the engine."""
+    eigenpairs on the host, the least-squares solve on the engine.  The tuple has no bcs: always the non-periodic system."""
     (i, eigenvalues, eigenvectors, q, pixels_per_dim, shape, acc, d0, d1, f_s, int_cond, xmin_bd, xmax_bd, ymin_bd, ymax_bd,
      reverse_dy) = args
     if acc not in ACCS:
@@ -386,9 +425,10 @@ def main(argv=None):
     ap.add_argument("--pixels-at-boundary", type=int, default=1)
     ap.add_argument("--reverse-dy", type=int, default=1)
     ap.add_argument("--acc", type=int, default=2, choices=ACCS, help="finite-difference order of the system (the model's fd_acc)")
+    ap.add_argument("--bcs", default="none", choices=BCS, help="boundary conditions of the system and the fields (the model's bcs)")
     ap.add_argument("--max-iter", type=int, default=None, help="default: MAX_ITER_ACC of the order")
     ap.add_argument("--iters-per-launch", type=int, default=None,
-                    help="acc 4 / 6: CGLS iterations per kernel launch for a batch of one workgroup per compute unit")
+                    help="acc 4 / 6, periodic: CGLS iterations per kernel launch for a batch of one workgroup per compute unit")
     ap.add_argument("--rtol", type=float, default=RTOL)
     ap.add_argument("--cache-dir", default=None, help="where the KLE basis is cached (default: not cached)")
     a = ap.parse_args(argv)
@@ -396,7 +436,7 @@ def main(argv=None):
     generate_darcy_dataset(a.n_samples, a.out, seed=a.seed, batch=a.batch, pixels_per_dim=a.pixels_per_dim, q=a.q,
                            length_scale=a.length_scale, pixels_at_boundary=bool(a.pixels_at_boundary),
                            reverse_dy=bool(a.reverse_dy), max_iter=a.max_iter, rtol=a.rtol, cache_dir=a.cache_dir, verbose=True,
-                           acc=a.acc, iters_per_launch=a.iters_per_launch)
+                           acc=a.acc, iters_per_launch=a.iters_per_launch, bcs=a.bcs)
     print(f"Data generation finished: {a.n_samples} samples in {time.time() - t0:.1f} s -> {a.out}")
 
 
