@@ -289,6 +289,22 @@ int pidm_darcy_gen_periodic(const double* basis, const double* z, int q, const d
  *                   across batch sizes.  x_new / u_out must not alias x / u; mesh tables 16-byte aligned.  2 <= nel <= 79 (the search direction and the moduli
  *                   live in LDS), rmin > 1, n_bisect >= 1, penal >= 1, 0 < e_min < 1.
  *                   workspace: pidm_simp_ws_bytes(nel, B).
+ *   pidm_simp_step_filtered: the same iteration in the three-field form: x are design variables, the density filter
+ *                   x~ = (H x) / Hs (H_ej as in step 4 above, Hs_e = sum_j H_ej) and, for filter = 2, the projection
+ *                   x^ = (tanh(beta eta) + tanh(beta (x~ - eta))) / (tanh(beta eta) + tanh(beta (1 - eta))) give the physical density
+ *                   (filter = 1: x^ = x~).  Launch, precision, `active`, reductions, limits and workspace as pidm_simp_step.  Per sample:
+ *                     1. x~, x^, d = dx^/dx~ (1, or beta (1 - tanh^2(beta (x~ - eta))) / (tanh(beta eta) + tanh(beta (1 - eta))),
+ *                        evaluated as beta / cosh^2(..) / (..));  E_e = e_min + x^_e^penal (1 - e_min)
+ *                     2. K_closed(E) u = f: the CG phase of pidm_simp_step, the same device function
+ *                     3. ce_e = u_e^T k_e u_e,  c = sum_e E_e ce_e,  g_e = -penal x^_e^(penal-1) (1 - e_min) max(ce_e, 0)
+ *                     4. dc_e = sum_j H_ej g_j d_j / Hs_j,  dv_e = sum_j H_ej d_j / Hs_j
+ *                     5. n_bisect bisection steps on lambda in [0, 1e9]:
+ *                        x_new = max(0, max(x - move, min(1, min(x + move, x sqrt(-dc / (dv lambda)))))),
+ *                        mean(x^(x~(x_new))) > vf => l1 = lambda, else l2 = lambda: every step filters and projects the trial design
+ *                        in LDS; the x_new of the last step is the result
+ *                   x_new [B, nel*nel] = the design variables, x_phys_new [B, nel*nel] = x^(x~(x_new)) (must not alias x / x_new),
+ *                   u_out, compliance = c, change = max |x_new - x|, pcg_iters, relres as pidm_simp_step.  An inactive sample is copied
+ *                   through and its x_phys_new is x^(x~(x)) at the given beta.  filter must be 1 or 2, beta > 0, 0 < eta < 1.
  *   pidm_mech_fields: nodal conditioning fields of a solved state u_dofs [B, ndof] (fp32, as pidm_mech_solve writes it) with Young's
  *                   moduli rho [B, nel*nel]: per element, at its centre, the strain energy density 1/2 rho_e u_e^T k_e u_e / area
  *                   and the plane-stress von Mises stress sqrt(sx^2 - sx sy + sy^2 + 3 txy^2), sigma = rho_e C(nu) B(0,0) u_e, for
@@ -299,6 +315,11 @@ int pidm_simp_step(const double* x, const double* u, const float* bcs, const flo
                    int kloc_stride, const int32_t* elem_dofs, const int32_t* dof_elems, int nel, double penal, double e_min,
                    double rmin, double move, int n_bisect, int pcg_max_iter, double pcg_rtol, double* x_new, double* u_out,
                    double* compliance, double* change, int32_t* pcg_iters, double* relres, void* workspace, int B, void* stream);
+int pidm_simp_step_filtered(const double* x, const double* u, const float* bcs, const float* vf, const int32_t* active,
+                            const float* kloc, int kloc_stride, const int32_t* elem_dofs, const int32_t* dof_elems, int nel, double penal,
+                            double e_min, double rmin, double move, int n_bisect, int pcg_max_iter, double pcg_rtol, int filter,
+                            double beta, double eta, double* x_new, double* x_phys_new, double* u_out, double* compliance,
+                            double* change, int32_t* pcg_iters, double* relres, void* workspace, int B, void* stream);
 int pidm_mech_fields(const float* u_dofs, const float* rho, const float* kloc, int kloc_stride, const int32_t* elem_dofs, int nel,
                      double nu, float* fields, int B, void* stream);
 

@@ -94,6 +94,8 @@ class PidmLib:
         d = C.c_double
         self._sig("pidm_simp_ws_bytes", [i, i], sz)
         self._sig("pidm_simp_step", [vp, vp, vp, vp, vp, vp, i, vp, vp, i, d, d, d, d, i, i, d, vp, vp, vp, vp, vp, vp, vp, i, vp])
+        self._sig("pidm_simp_step_filtered", [vp, vp, vp, vp, vp, vp, i, vp, vp, i, d, d, d, d, i, i, d, i, d, d, vp, vp, vp, vp, vp, vp, vp,
+                                              vp, i, vp])
         self._sig("pidm_mech_fields", [vp, vp, vp, i, vp, i, d, vp, i, vp])
         self._sig("pidm_unet_num_cond_params", [vp])
         self._sig("pidm_unet_enable_cond", [vp, i])

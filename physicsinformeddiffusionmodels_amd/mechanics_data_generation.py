@@ -7,6 +7,9 @@ minimiser, one `pidm_simp_step` launch per iteration (csrc/k_mech_gen.hip: fp64 
 optimality-criteria update, one workgroup per sample), then a final FE solve of the stored field under the training operator
 (`pidm_mech_solve`) and the two conditioning fields of the uniform domain (`pidm_mech_fields`).  DESIGN.md section 4b.  Host-side
 pieces are the random problem draw and the file writing.  There is no CPU fallback.
+`filter='density'` / `'heaviside'` run the three-field form instead (`pidm_simp_step_filtered`: design variables -> density filter
+-> tanh projection with beta continuation), whose near-binary result the 0.5 cut hardly changes; `binarize='volume'` makes the stored
+solid fraction equal vf.  The defaults write the files they always wrote.
 
 Support scenarios of `sample_problem` (node grid [row, col], row 0 is the top edge; every one removes the three rigid-body modes):
   0  left edge clamped              1  right edge clamped
@@ -129,12 +132,28 @@ def _check_converged(relres, rtol, labels, what="mechanics solve"):
         raise PidmError(f"{what} did not converge (||r|| / ||f|| > {rtol:g}) for sample(s) {bad}: raise pcg_max_iter")
 
 
+FILTERS = {"sensitivity": 0, "density": 1, "heaviside": 2}   # the `filter` argument -> pidm_simp_step (0) / pidm_simp_step_filtered's mode
+
+
+def _check_filter(who, filter, beta, eta):
+    if filter not in FILTERS:
+        raise PidmError(f"{who}: unknown filter {filter!r} (one of {', '.join(FILTERS)})")
+    if not beta > 0:
+        raise PidmError(f"{who}: beta={beta} must be positive")
+    if not 0 < eta < 1:
+        raise PidmError(f"{who}: eta={eta} must lie in (0, 1)")
+    return FILTERS[filter]
+
+
 def simp_step(x, u, bcs, vf, nel, *, active=None, penal=3., e_min=1e-3, rmin=1.5, move=0.2, n_bisect=60, pcg_rtol=1e-8,
-              pcg_max_iter=20000, out=None, lib=None):
+              pcg_max_iter=20000, out=None, lib=None, filter="sensitivity", beta=1., eta=0.5):
     """One `pidm_simp_step`: (x [B,E], u [B,ndof]) fp64 -> dict(x, u, compliance, change, pcg_iters, relres) of new tensors (or the
-    ones given in `out`, whose scalar entries of inactive samples are left untouched)."""
+    ones given in `out`, whose scalar entries of inactive samples are left untouched).
+    filter = 'density' / 'heaviside': one `pidm_simp_step_filtered` (density filter; plus the tanh projection at `beta`, `eta`).  x are
+    the design variables then, and the dict gains x_phys [B,E], the physical (filtered, projected) density of the new design."""
     if not isinstance(x, torch.Tensor):
         raise PidmError("simp_step: x must be a torch tensor on the device")
+    mode = _check_filter("simp_step", filter, beta, eta)
     device, lib = _resolve(x.device, lib)
     st = _mesh(nel, device)
     B = x.shape[0]
@@ -153,27 +172,40 @@ def simp_step(x, u, bcs, vf, nel, *, active=None, penal=3., e_min=1e-3, rmin=1.5
     ws = out.get("ws")
     if ws is None:
         ws = out["ws"] = torch.empty(lib.pidm_simp_ws_bytes(nel, B), dtype=torch.uint8, device=device)
-    lib.check(lib.pidm_simp_step(ptr(x), ptr(u), ptr(bcs), ptr(vf), ptr(active), ptr(st.kloc_dev), st.kloc_stride, ptr(st.elem_dofs32),
-                                 ptr(st.dof_elems32), nel, float(penal), float(e_min), float(rmin), float(move), int(n_bisect),
-                                 int(pcg_max_iter), float(pcg_rtol), ptr(out["x"]), ptr(out["u"]), ptr(out["compliance"]),
-                                 ptr(out["change"]), ptr(out["pcg_iters"]), ptr(out["relres"]), ptr(ws), B, stream_ptr(device)),
-              "pidm_simp_step")
+    head = (ptr(x), ptr(u), ptr(bcs), ptr(vf), ptr(active), ptr(st.kloc_dev), st.kloc_stride, ptr(st.elem_dofs32), ptr(st.dof_elems32), nel,
+            float(penal), float(e_min), float(rmin), float(move), int(n_bisect), int(pcg_max_iter), float(pcg_rtol))
+    tail = (ptr(out["u"]), ptr(out["compliance"]), ptr(out["change"]), ptr(out["pcg_iters"]), ptr(out["relres"]), ptr(ws), B,
+            stream_ptr(device))
+    if mode == 0:
+        lib.check(lib.pidm_simp_step(*head, ptr(out["x"]), *tail), "pidm_simp_step")
+    else:
+        if out.get("x_phys") is None:
+            out["x_phys"] = torch.empty_like(x)
+        lib.check(lib.pidm_simp_step_filtered(*head, mode, float(beta), float(eta), ptr(out["x"]), ptr(out["x_phys"]), *tail),
+                  "pidm_simp_step_filtered")
     return out
 
 
 def simp_optimize(bcs, vf, nel, *, penal=3., e_min=1e-3, rmin=1.5, move=0.2, n_bisect=60, max_iter=100, tol=0.01, pcg_rtol=1e-8,
-                  pcg_max_iter=20000, check_every=5, labels=None, device=None, lib=None):
+                  pcg_max_iter=20000, check_every=5, labels=None, device=None, lib=None, filter="sensitivity", beta_max=8., beta_every=25,
+                  eta=0.5):
     """SIMP compliance minimisation of a batch: starts from x = vf, u = 0 and calls `pidm_simp_step` until every sample's
     change = max |x_new - x| is below tol, or max_iter.  change is read back only every check_every iterations; samples that are
     done are switched off (`active`) and cost nothing afterwards.  bcs [B,4,nn,nn] float32, vf [B].
     Returns (x [B,E] fp64, u [B,ndof] fp64, compliance history [iterations,B] fp64 (NaN where a sample was already done),
     dict(simp=[B] SIMP iterations per sample, pcg=[iterations,B] CG iterations of every step)), all on the device.
+    filter = 'density' / 'heaviside' (`pidm_simp_step_filtered`): the first tensor is the physical density of the last design and
+    the design variables are the dict's 'design'.  'heaviside' runs iteration k (from 0) at beta = min(beta_max, 2^(k // beta_every))
+    for the whole batch, and change < tol switches a sample off only once beta has reached beta_max.
     Raises PidmError naming the samples whose solve ended above pcg_rtol."""
     if not isinstance(bcs, torch.Tensor):
         bcs = torch.from_numpy(np.asarray(bcs, dtype=np.float32))
     device, lib = _resolve(device if device is not None else bcs.device, lib)
     if max_iter < 1 or check_every < 1:
         raise PidmError("simp_optimize: max_iter and check_every must be >= 1")
+    mode = _check_filter("simp_optimize", filter, beta_max, eta)
+    if mode == 2 and beta_every < 1:
+        raise PidmError("simp_optimize: beta_every must be >= 1")
     st = _mesh(nel, device)
     bcs = bcs.to(device=device, dtype=torch.float32).contiguous()
     B = bcs.shape[0]
@@ -193,11 +225,17 @@ def simp_optimize(bcs, vf, nel, *, penal=3., e_min=1e-3, rmin=1.5, move=0.2, n_b
     n_simp = np.zeros(B, dtype=np.int64)
     alive = np.ones(B, dtype=bool)
     ws = None
+    x_phys = torch.empty_like(x) if mode else None
+    beta = float(beta_max)
     done, checked = 0, 0
     for it in range(max_iter):
         out = dict(x=x2, u=u2, compliance=comp[it], change=change, pcg_iters=pcg[it], relres=relres[it], ws=ws)
+        if mode:
+            out["x_phys"] = x_phys
+        if mode == 2:
+            beta = min(float(beta_max), 2. ** (it // beta_every))
         simp_step(x, u, bcs, vf, nel, active=active, penal=penal, e_min=e_min, rmin=rmin, move=move, n_bisect=n_bisect,
-                  pcg_rtol=pcg_rtol, pcg_max_iter=pcg_max_iter, out=out, lib=lib)
+                  pcg_rtol=pcg_rtol, pcg_max_iter=pcg_max_iter, out=out, lib=lib, filter=filter, beta=beta, eta=eta)
         ws = out["ws"]
         x, x2, u, u2 = x2, x, u2, u
         done = it + 1
@@ -205,11 +243,15 @@ def simp_optimize(bcs, vf, nel, *, penal=3., e_min=1e-3, rmin=1.5, move=0.2, n_b
         if done % check_every == 0 or done == max_iter:
             _check_converged(relres[checked:done].max(dim=0).values.cpu().numpy(), pcg_rtol, labels)
             checked = done
-            alive &= ~(change.cpu().numpy() < tol)
+            if beta >= beta_max:           # (the continuation is not over before: a design that rests at a lower beta is not done)
+                alive &= ~(change.cpu().numpy() < tol)
             if not alive.any():
                 break
             active.copy_(torch.from_numpy(alive.astype(np.int32)))
     iters = dict(simp=torch.from_numpy(n_simp).to(device), pcg=pcg[:done])
+    if mode:
+        iters["design"] = x
+        return x_phys, u, comp[:done], iters
     return x, u, comp[:done], iters
 
 
@@ -243,13 +285,32 @@ def mech_fields(u_dofs, rho, nel, lib=None):
     return out
 
 
+def _binarize(x, vf, how):
+    """E_field [B,E] float32 of the density x [B,E]: True / 'threshold' cuts at 0.5, 'volume' keeps the round(vf E) densest elements of
+    every sample (ties go to the lower element index), False stores clip(x, E_VOID, 1)."""
+    if how is False:
+        return x.clamp(E_VOID, 1.0).float().contiguous()
+    if how is True or how == "threshold":
+        return torch.where(x > 0.5, 1.0, E_VOID).float().contiguous()
+    E = x.shape[1]
+    order = torch.sort(x, dim=1, descending=True, stable=True).indices
+    k = torch.round(vf.double() * E).long().view(-1, 1)
+    solid = torch.zeros_like(x, dtype=torch.bool).scatter_(1, order, torch.arange(E, device=x.device).view(1, E) < k)
+    return torch.where(solid, 1.0, E_VOID).float().contiguous()
+
+
 def generate_mechanics_batch(seeds, nel=64, binarize=True, n_loads=1, final_rtol=FINAL_RTOL, return_info=False, device=None, lib=None,
-                             **simp):
+                             filter="sensitivity", **simp):
     """Samples for the given seeds, [B,10,nn,nn] float32 on the device in the reference's channel order: vf (constant image),
     strain energy density and von Mises stress of the uniform domain E = 1 under the sample's supports and loads, disp_x, disp_y,
     E_field (zero-padded to nn: last row and column 0), BC_node_x, BC_node_y, load_x, load_y.  E_field = where(x > 0.5, 1, 1e-3)
     of the SIMP result (clip(x, 1e-3, 1) without `binarize`); the displacements are the FE solution of exactly that field under
-    the training operator.  `simp`: keyword arguments of simp_optimize."""
+    the training operator.  binarize = 'volume': E_field is 1 on the round(vf E) elements of largest density instead, so that its solid
+    fraction is vf to half an element.  `filter` and `simp`: keyword arguments of simp_optimize; with filter = 'density' / 'heaviside'
+    x is the physical density, which return_info's dict then holds as 'x_phys' ([B,E] fp64; the design variables are iters['design'])."""
+    if not (isinstance(binarize, bool) or binarize in ("threshold", "volume")):
+        raise PidmError(f"generate_mechanics_batch: binarize={binarize!r} must be True, False, 'threshold' or 'volume'")
+    _check_filter("generate_mechanics_batch", filter, simp.get("beta_max", 8.), simp.get("eta", 0.5))
     device, lib = _resolve(device, lib)
     seeds = [int(s) for s in seeds]
     B, nn = len(seeds), nel + 1
@@ -259,11 +320,8 @@ def generate_mechanics_batch(seeds, nel=64, binarize=True, n_loads=1, final_rtol
     probs = [sample_problem(s, nel, n_loads) for s in seeds]
     bcs = torch.from_numpy(np.stack([p[0] for p in probs])).to(device)
     vf = torch.tensor([p[1] for p in probs], dtype=torch.float32, device=device)
-    x, _, comp, iters = simp_optimize(bcs, vf, nel, labels=labels, device=device, lib=lib, **simp)
-    if binarize:
-        E_field = torch.where(x > 0.5, 1.0, E_VOID).float().contiguous()
-    else:
-        E_field = x.clamp(E_VOID, 1.0).float().contiguous()
+    x, _, comp, iters = simp_optimize(bcs, vf, nel, labels=labels, device=device, lib=lib, filter=filter, **simp)
+    E_field = _binarize(x, vf, binarize)
     st = _mesh(nel, device)
     max_iter = simp.get("pcg_max_iter", 20000)
     u = _fe_solve(lib, st, nel, E_field, bcs, final_rtol, max_iter, labels, "final mechanics solve")
@@ -277,14 +335,17 @@ def generate_mechanics_batch(seeds, nel=64, binarize=True, n_loads=1, final_rtol
     out[:, 6:10] = bcs
     if device.type == "cuda":
         torch.cuda.synchronize(device)
-    return (out, dict(compliance=comp, iters=iters)) if return_info else out
+    info = dict(compliance=comp, iters=iters)
+    if filter != "sensitivity":
+        info["x_phys"] = x
+    return (out, info) if return_info else out
 
 
 def generate_mechanics_dataset(n_samples, out_dir, seed=None, seeds=None, batch=256, nel=64, n_loads=1, binarize=True, device=None,
-                               lib=None, verbose=False, **simp):
+                               lib=None, verbose=False, filter="sensitivity", **simp):
     """Writes out_dir/<i>.npy, i = 0 .. n_samples-1, each [nn,nn,10] float32 - what `Dataset_Paths` reads (it transposes to
     [10,nn,nn] and sorts by the integer name).  `seeds` (explicit, must be distinct) or `seed` (draws n_samples distinct seeds
-    reproducibly); neither: fresh ones.  Returns the seeds."""
+    reproducibly); neither: fresh ones.  `binarize`, `filter` and `simp` as in generate_mechanics_batch.  Returns the seeds."""
     if seeds is None:
         seeds = _unique_seeds(n_samples, seed)
     seeds = [int(s) for s in seeds]
@@ -299,7 +360,8 @@ def generate_mechanics_dataset(n_samples, out_dir, seed=None, seeds=None, batch=
     os.makedirs(out_dir, exist_ok=True)
     t0 = time.time()
     for lo in range(0, n_samples, batch):
-        data, info = generate_mechanics_batch(seeds[lo:lo + batch], nel, binarize, n_loads, return_info=True, device=device, lib=lib, **simp)
+        data, info = generate_mechanics_batch(seeds[lo:lo + batch], nel, binarize, n_loads, return_info=True, device=device, lib=lib,
+                                              filter=filter, **simp)
         arr = data.permute(0, 2, 3, 1).contiguous().cpu().numpy()
         for k in range(arr.shape[0]):
             np.save(os.path.join(out_dir, f"{lo + k}.npy"), arr[k])
@@ -319,10 +381,18 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--max-iter", type=int, default=100, help="SIMP iterations at most")
     ap.add_argument("--no-binarize", action="store_true", help="store clip(x, 1e-3, 1) instead of the 0.5-thresholded field")
+    ap.add_argument("--filter", choices=sorted(FILTERS, key=FILTERS.get), default="sensitivity",
+                    help="sensitivity filter (default), density filter, or density filter + tanh projection with beta continuation")
+    ap.add_argument("--beta-max", type=float, default=8., help="heaviside: the projection's beta doubles from 1 up to this")
+    ap.add_argument("--beta-every", type=int, default=25, help="heaviside: SIMP iterations per beta")
+    ap.add_argument("--binarize", choices=["threshold", "volume"], default="threshold",
+                    help="threshold: cut at 0.5; volume: keep the round(vf E) densest elements (solid fraction = vf)")
     a = ap.parse_args(argv)
     t0 = time.time()
+    extra = dict(beta_max=a.beta_max, beta_every=a.beta_every) if a.filter == "heaviside" else {}
     generate_mechanics_dataset(a.n_samples, a.out, seed=a.seed, batch=a.batch, nel=a.nel, n_loads=a.n_loads,
-                               binarize=not a.no_binarize, max_iter=a.max_iter, verbose=True)
+                               binarize=False if a.no_binarize else (True if a.binarize == "threshold" else a.binarize),
+                               max_iter=a.max_iter, verbose=True, filter=a.filter, **extra)
     print(f"Data generation finished: {a.n_samples} samples in {time.time() - t0:.1f} s -> {a.out}")
 
 
