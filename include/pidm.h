@@ -137,6 +137,29 @@ int pidm_psample_update(const float* x0_pred, const float* x_t, const float* z, 
                         float* x_prev, size_t n, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Posterior guidance of the Darcy sampler (csrc/k_guidance.hip; no counterpart in the reference: an extension).
+ * Per sample, with x = the x0 estimate, y = observations, m = 0/1 mask (all [B,2,P,P], channel 0 = p, 1 = K):
+ *   L_obs = sum m (x - y)^2,  L_pde = sum r(x)^2 over the three residual channels,
+ *   Phi = zeta_obs sqrt(L_obs) + zeta_pde sqrt(L_pde),  v = dPhi/dx (a term whose L is exactly 0 is omitted: no NaN, no epsilon).
+ * sums [B,2] = (L_obs, L_pde), fp32 roundings of fp64 fixed-tree sums: bit-identical run to run and across batch sizes.
+ *
+ * pidm_darcy_guidance_cotangent: second-order, non-periodic stencils (the kernel of pidm_darcy_residual_fwd / _bwd), v and sums in
+ * ONE launch, one workgroup per sample with the sample and its adjoint operands resident in LDS: 5 <= P <= 71 (8 P^2 floats of
+ * LDS); anything else fails with a message. */
+int pidm_darcy_guidance_cotangent(const float* x0_pred, const float* obs, const float* mask, const float* f_s, float inv_h0,
+                                  float inv_h1, float zeta_obs, float zeta_pde, float* v, float* sums, int B, int P, void* stream);
+/* Any stencil set: sits between pidm_darcy_residual_general_fwd (-> residual [B,P*P,3]) and _bwd.  Writes sums, grad_res =
+ * zeta_pde r / sqrt(L_pde) (the input of the general adjoint) and v_obs = the observation part of v; pidm_guidance_add then adds
+ * the adjoint's result: v[i] += adjoint[i], n elements. */
+int pidm_guidance_scale_general(const float* x0_pred, const float* obs, const float* mask, const float* residual, float zeta_obs,
+                                float zeta_pde, float* grad_res, float* v_obs, float* sums, int B, int P, void* stream);
+int pidm_guidance_add(float* v, const float* adjoint, size_t n, void* stream);
+/* guided ancestral update x_{t-1} = c1 x0_pred + c2 x_t + sigma z - g; g [B,HW,C] is the UNet's input-gradient layout
+ * (pidm_unet_backward_input), read transposed; everything else [B,C,HW].  C <= 16. */
+int pidm_psample_update_guided(const float* x0_pred, const float* x_t, const float* z, const float* g_nhwc, float c1, float c2,
+                               float sigma, float* x_prev, int B, int C, int HW, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Fused global-norm clip + Adam over flat fp32 buffers    replaces main.py:165-166
  *   torch.nn.utils.clip_grad_norm_(model.parameters(), 1.) ; optimizer.step()   (torch.optim.Adam, no weight decay/amsgrad)
  * param/grad/exp_avg/exp_avg_sq: n floats each, 16-byte aligned; `step` is the 1-based update count (bias correction);
@@ -375,6 +398,15 @@ int pidm_unet_set_condition(pidm_unet* h, const float* cond_nhwc);
 /* grad_out: [B,out_dim,P,P] NCHW.  grad_x (may be NULL): [B,P*P,C].  Writes all bound grads. */
 int pidm_unet_backward(pidm_unet* h, const float* grad_out_nchw, float* grad_x_nhwc, int B, void* workspace,
                        size_t workspace_bytes, void* stream);
+/* The input gradient alone (posterior guidance: the gradient of a potential of the x0 estimate with respect to x_t).  Same tape
+ * contract as pidm_unet_backward (follows a save_for_backward forward of the same B, no conditioning input) and the same
+ * input-gradient chain - same kernels, arguments and arena layout, so grad_x is bit-identical to pidm_unet_backward's - but no
+ * convolution weight-gradient kernel, no time-MLP / FiLM backward, no gradient reduction, no side stream and no phase events.
+ * Parameter-gradient by-products of the data-path kernels (GroupNorm / LayerNorm / attention-projection partials) stay in the
+ * workspace; nothing is written through the gradient pointers of pidm_unet_bind, which may be NULL.  Replayed as a hipGraph of
+ * its own from the third identical call on.  grad_x is required. */
+int pidm_unet_backward_input(pidm_unet* h, const float* grad_out_nchw, float* grad_x_nhwc, int B, void* workspace,
+                             size_t workspace_bytes, void* stream);
 
 /* Data-parallel overlap (no reference counterpart: the reference is single-process).  The deferred gradient
  * reduction of pidm_unet_backward runs in n_phases (1..3) launches - after the decoder half (ups.*, final_conv.*), after the

@@ -37,6 +37,7 @@ class UnetEngine:
         cfg.self_condition = int(bool(model.self_condition))
         cfg.padding_mode = {'zeros': 0, 'circular': 1}[getattr(model, 'padding_mode', 'zeros')]
         self.image_size = image_size
+        self.in_channels = model.channels * (2 if model.self_condition else 1)
         self.handle = vp()
         self.lib.check(self.lib.pidm_unet_create(C.byref(cfg), C.byref(self.handle)), "pidm_unet_create")
         n = self.lib.pidm_unet_num_params(self.handle)
@@ -124,13 +125,16 @@ class UnetEngine:
 
     # ---- forward / backward ------------------------------------------------------------------------------
     def forward(self, x_nhwc: torch.Tensor, t: torch.Tensor, training: bool, repack: bool = True,
-                cond: torch.Tensor | None = None, early: bool = False, frozen=None) -> torch.Tensor:
-        """`frozen`: the token of an enclosing `frozen_weights(model)` scope (None outside one).  Inside such a scope the
+                cond: torch.Tensor | None = None, early: bool = False, frozen=None, need_grad: bool | None = None) -> torch.Tensor:
+        """`need_grad=False` with `training=True`: a tape for `backward_input` only - no gradient buffer is created or bound, and
+        the forward counts as an inference forward for the `frozen` rule below.
+        `frozen`: the token of an enclosing `frozen_weights(model)` scope (None outside one).  Inside such a scope the
         caller guarantees constant parameters, so only the scope's first inference forward of this engine re-packs (and
         re-splits) the weights; everywhere else every forward does (the parameters may have been written by anything)."""
         B = x_nhwc.shape[0]
         dev = x_nhwc.device
-        self._ensure_bound(training, early=early)
+        tape_only = training and need_grad is False
+        self._ensure_bound(training and not tape_only, early=early)
         if cond is not None:
             if not self.cond_enabled:          # size the workspace for the conditioning branch from now on
                 self.lib.check(self.lib.pidm_unet_enable_cond(self.handle, 1), "pidm_unet_enable_cond")
@@ -141,7 +145,7 @@ class UnetEngine:
         out = torch.empty(B, self.lib_out_dim, P, P, dtype=torch.float32, device=dev)
         base = ws.data_ptr()
         al = (-base) % 256
-        if frozen is not None and not training and repack:
+        if frozen is not None and (not training or tape_only) and repack:
             key = (frozen, self._bound_key, base)
             repack = key != self._packed_for     # same scope, same parameter storage, same workspace: the packed weights are current
             self._packed_for = key
@@ -160,6 +164,21 @@ class UnetEngine:
         al = (-base) % 256
         self.lib.check(self.lib.pidm_unet_backward(self.handle, ptr(grad_out), ptr(gx), B, vp(base + al), ws.numel() - al,
                                                    stream_ptr(dev)), "pidm_unet_backward")
+        return gx
+
+    def backward_input(self, grad_out: torch.Tensor) -> torch.Tensor:
+        """d <grad_out, out> / d x [B,P*P,C] of the latest training-mode forward through pidm_unet_backward_input: the input-gradient
+        chain alone - no weight gradient is computed and no gradient buffer is read, written or needed."""
+        B = grad_out.shape[0]
+        dev = grad_out.device
+        ws = self.workspace
+        if ws is None:
+            raise PidmError("backward_input: no forward has run on this engine")
+        gx = torch.empty(B, self.image_size * self.image_size, self.in_channels, dtype=torch.float32, device=dev)
+        base = ws.data_ptr()
+        al = (-base) % 256
+        self.lib.check(self.lib.pidm_unet_backward_input(self.handle, ptr(grad_out), ptr(gx), B, vp(base + al), ws.numel() - al,
+                                                         stream_ptr(dev)), "pidm_unet_backward_input")
         return gx
 
 
@@ -356,3 +375,58 @@ def unet_apply(model, x, time, lib: PidmLib | None = None, cond=None, x_self_con
     if video:
         out = out.unsqueeze(2)
     return out
+
+
+GUIDE_SLOT = "input-gradient"
+
+
+def input_gradient_pass(model, x, t, lib: PidmLib | None = None, cond=None):
+    """x0_pred = model(x, t) together with a pull-back to the input, without touching any parameter gradient.
+
+    x: [B,P*P,C] or [B,C,P,P]; t: int64 [B].  Returns `(x0_pred [B,C,P,P], pull)` with `pull(cotangent [B,C,P,P]) -> [B,P*P,C]` =
+    d <cotangent, x0_pred> / d x.  Works under `torch.no_grad()`; nothing is recorded by autograd.  The pass runs on an engine slot
+    of its own (own handle, workspace and activation tape, NO gradient buffer), so a pending training tape of `model`, every `p.grad`
+    and the flat gradient buffer stay bit-unchanged, and `pull` computes no weight gradient (pidm_unet_backward_input).  `pull`
+    refers to the latest pass of this model only.  Inside `frozen_weights(model)` the weights are packed for the first pass only.
+    Conditioning inputs, self-conditioning models and multi-frame inputs are not supported."""
+    if cond is not None:
+        raise PidmError("input_gradient_pass: cond= (the gradient-guidance conditioning branch) is not supported")
+    if model.self_condition:
+        raise PidmError("input_gradient_pass: self-conditioning models are not supported")
+    if x.dim() == 3:
+        B, N, Cc = x.shape
+        P = int(math.isqrt(N))
+        if P * P != N:
+            raise ValueError('Input [B, P*P, C] needs a square number of pixels.')
+        x_nhwc = x
+    elif x.dim() == 4:
+        B, Cc, P, P2 = x.shape
+        if P != P2:
+            raise ValueError('Input [B, C, P, P] must be square.')
+        x_nhwc = x.permute(0, 2, 3, 1).reshape(B, P * P, Cc)
+    else:
+        raise PidmError("input_gradient_pass: input must be [B,P*P,C] or [B,C,P,P] (multi-frame input is not supported)")
+    if Cc != model.channels:
+        raise ValueError(f'expected {model.channels} input channels, got {Cc}')
+    if lib is None:
+        lib = getattr(model, "_pidm_lib", None)
+    if lib is None and not x.is_cuda:
+        raise PidmError("input_gradient_pass needs tensors on an MI355X (cuda device): the gfx950 engine has no CPU fallback")
+    x_nhwc = x_nhwc.detach().contiguous().float()
+    tt = t.to(device=x.device, dtype=torch.int64).contiguous()
+    if tt.numel() != B:
+        raise ValueError('time must have one entry per batch element')
+    eng = get_engine(model, P, lib, GUIDE_SLOT)
+    eng.tape_generation += 1
+    generation = eng.tape_generation
+    out = eng.forward(x_nhwc, tt, training=True, need_grad=False, frozen=getattr(model, "_pidm_frozen", None))
+
+    def pull(cotangent):
+        if eng.tape_generation != generation:
+            raise PidmError("input_gradient_pass: pull() of an earlier pass (a later pass of this model overwrote its tape)")
+        if tuple(cotangent.shape) != tuple(out.shape):
+            raise ValueError(f'cotangent must be {tuple(out.shape)}, got {tuple(cotangent.shape)}')
+        keep = (x_nhwc, tt, out)   # the tape holds raw pointers to these  # noqa: F841
+        return eng.backward_input(cotangent.detach().contiguous().float())
+
+    return out, pull

@@ -77,6 +77,10 @@ class PidmLib:
         self._sig("pidm_qsample_nhwc", [vp, vp, vp, vp, vp, i, i, i, vp])
         self._sig("pidm_qsample_nhwc_t", [vp, vp, vp, vp, vp, vp, i, i, i, vp])
         self._sig("pidm_psample_update", [vp, vp, vp, f, f, f, vp, sz, vp])
+        self._sig("pidm_psample_update_guided", [vp, vp, vp, vp, f, f, f, vp, i, i, i, vp])
+        self._sig("pidm_darcy_guidance_cotangent", [vp, vp, vp, vp, f, f, f, f, vp, vp, i, i, vp])
+        self._sig("pidm_guidance_scale_general", [vp, vp, vp, vp, f, f, vp, vp, vp, i, i, vp])
+        self._sig("pidm_guidance_add", [vp, vp, sz, vp])
         self._sig("pidm_mech_apply", [vp, vp, vp, vp, i, vp, vp, i, vp, vp, i, vp])
         self._sig("pidm_mech_solve_ws_bytes", [i, i], sz)
         self._sig("pidm_mech_solve", [vp, vp, vp, i, vp, vp, i, f, f, f, i, C.c_double, vp, vp, vp, vp, vp, vp, i, vp])
@@ -120,6 +124,7 @@ class PidmLib:
         self._sig("pidm_unet_bind", [vp, C.POINTER(vp), C.POINTER(vp)])
         self._sig("pidm_unet_forward", [vp, vp, vp, vp, i, i, i, vp, sz, vp])
         self._sig("pidm_unet_backward", [vp, vp, vp, i, vp, sz, vp])
+        self._sig("pidm_unet_backward_input", [vp, vp, vp, i, vp, sz, vp])
         self._sig("pidm_unet_set_grad_events", [vp, i, C.POINTER(vp)])
         self._sig("pidm_unet_grad_phase_range", [vp, i, i, C.POINTER(C.c_int), C.POINTER(C.c_int)])
         self._sig("pidm_conv_packed_weight_floats", [C.POINTER(ConvDesc)], sz)

@@ -188,8 +188,8 @@ struct pidm_unet {
   // hipGraph replay
   hipStream_t cap_stream = nullptr;                      // private capture stream (the caller's may be the null stream, which cannot capture)
   bool cap_stream_ok = false;
-  std::vector<GraphEntry> graphs[2];                     // [0] forward, [1] backward
-  std::vector<std::vector<uint64_t>> seen[2];            // keys seen once (captured on their second sighting)
+  std::vector<GraphEntry> graphs[3];                     // [0] forward, [1] backward, [2] input-only backward
+  std::vector<std::vector<uint64_t>> seen[3];            // keys seen once (captured on their second sighting)
   uint64_t graph_stamp = 0, bind_sig = 0, param_sig = 0, fwd_key_hash = 0;
   uint64_t arena_sig = 0;                                // layout of the latest pass that used the workspace arena
   uint64_t red_table_owner = 0;                          // layout that uploaded the reduction descriptor table
@@ -258,6 +258,11 @@ struct Run {
   bool group_on = false;
   bool defer_on = false;
   bool overlap = false;        // weight gradients on the side stream (real backward runs only)
+  // pidm_unet_backward_input: the input-gradient chain alone.  Same kernels, same arguments and the same arena layout as the full
+  // pass (the plan is the full pass's), but no weight-gradient problem is launched or queued, the time path is left out and the
+  // queued parameter-gradient reductions never run: their partials stay in the deferred arena (engine-private), so nothing is
+  // written through U->G
+  bool input_only = false;
   // Backward arena frames are kept to the end of the pass while side-stream weight gradients may still read them; the sizing dry
   // run assumes that only where a real pass can take the side stream at all (PIDM_GRAPH=0: captured passes are linear, and with
   // graph replay on - the default - the two eager passes before the capture are linear too), otherwise frames are recycled and
@@ -517,7 +522,7 @@ extern "C" int pidm_unet_create(const pidm_unet_cfg* cfg, pidm_unet** out) {
 
 extern "C" void pidm_unet_destroy(pidm_unet* h) {
   if (!h) return;
-  for (int k = 0; k < 2; ++k)
+  for (int k = 0; k < 3; ++k)
     for (auto& e : h->graphs[k]) pidm::graph_entry_free(e);
   if (h->cap_stream_ok) (void)hipStreamDestroy(h->cap_stream);
   if (h->side_ok) {
@@ -985,7 +990,7 @@ static int flush_wgrads(Run& r) {
 // ld_dy: channel stride of dy (0 = L.Cout, contiguous): the two halves of a concatenation's gradient are read in place
 static int conv_wgrad(Run& r, const ConvLayer& L, const float* x0, const float* x1, const float* dy, int ld_dy = 0) {
   pidm_unet* U = r.U;
-  if (!U->have_grads && !r.dry) return 0;
+  if ((!U->have_grads || r.input_only) && !r.dry) return 0;
   if (!ld_dy) ld_dy = L.Cout;
   ConvGeom g;
   const int Ho = out_h(L);
@@ -1138,6 +1143,7 @@ static int attn_bwd(Run& r, AttnBlock& a, const float* g_out, float* g_x, const 
   float* g_qkv = nullptr;
   float* g_xn = nullptr;
   bool out_bias_with_ln = false;
+  const bool param_grads = U->have_grads && !r.dry && !r.input_only;
   if (r.dry ? attn_projected(a, heads) : a.projected) {
     // no qkv tensor, no dqkv tensor: d_xn and the to_qkv / to_out weight-gradient shares come straight from (xn, dY)
     const size_t nr = (size_t)B * lap_dw_ranges(N, C);
@@ -1149,7 +1155,7 @@ static int attn_bwd(Run& r, AttnBlock& a, const float* g_out, float* g_x, const 
     g_xn = r.tmp.alloc(npix * C);
     RUN(launch_lap_backward(a.xn, g_out, U->P[a.qkv.w], U->P[a.out.w], a.lsaved, a.qstat, g_xn, dwqk, dwv, dwo, ltmp, C, B, N, heads, r.scratch,
                             r.st));
-    if (U->have_grads && !r.dry) {
+    if (param_grads) {
       float* gw = U->G[a.qkv.w];
       if (r.q()) {
         r.q()->push(dwqk, gw, nullptr, nullptr, (size_t)2 * HD * C, (int)nr, 2 * HD, C, 1, 2 * HD, C);
@@ -1164,7 +1170,7 @@ static int attn_bwd(Run& r, AttnBlock& a, const float* g_out, float* g_x, const 
     // the to_out bias gradient (column sums of g_out) rides with the LayerNorm backward, which reads g_out as its residual share
     float* ln_part = r.part_alloc(layernorm_bwd_ws_bytes(C) + colsum_ws_bytes(1024, C));
     RUN(launch_layernorm_bwd(a.x, U->P[a.gamma], g_xn, g_out, g_x, U->G[a.gamma], npix, C, ln_part, r.st, r.q(),
-                             (U->have_grads && !r.dry) ? U->G[a.out.b] : nullptr, gn_x, gn_st, gn_gm, gn_bt, U->groups, B, N, gn_part));
+                             param_grads ? U->G[a.out.b] : nullptr, gn_x, gn_st, gn_gm, gn_bt, U->groups, B, N, gn_part));
     if (pc_prev) *pc_prev = gn_pc;
     if (!r.keep_frames()) r.tmp.release(mk);
     return 0;
@@ -1179,7 +1185,7 @@ static int attn_bwd(Run& r, AttnBlock& a, const float* g_out, float* g_x, const 
     float* dwpart = r.defer_on ? r.defer.alloc(dwn) : r.tmp.alloc(dwn);
     RUN(launch_la_backward_fused(a.qkvb, a.kstat, a.qstat, a.ctx, g_out, C, U->P[a.out.w], C, dctx, rowdot, g_qkv, dwpart, B, N,
                                  heads, r.scratch, r.st));
-    if (U->have_grads && !r.dry) {
+    if (param_grads) {
       if (r.q()) r.q()->push(dwpart, U->G[a.out.w], nullptr, nullptr, (size_t)C * HD, B, C, HD, 1, C, HD);
       else RUN(launch_split_reduce(dwpart, U->G[a.out.w], nullptr, nullptr, B, C, HD, 1, C, HD, r.st));
       if (a.out.b >= 0) out_bias_with_ln = true;      // column sums of g_out: with the LayerNorm backward below
@@ -1359,14 +1365,14 @@ static int backward_impl(Run& r, const float* grad_out_nchw, float* grad_x_nhwc)
   size_t red_done = 0;
   r.wq.clear();
   r.wq_dev = reinterpret_cast<WgradItem*>(r.defer.alloc(kWgFams * kMaxWgradItems * sizeof(WgradItem) / 4));
-  const int n_phases = U->n_phases;
+  const int n_phases = r.input_only ? 1 : U->n_phases;   // (the input-only pass flushes nothing and records no phase event)
   float* dss = r.tmp.alloc((size_t)B * U->ss_total);
   float* g_o = r.tmp.alloc((size_t)B * HW * od);
   RUN(launch_nchw_to_nhwc(grad_out_nchw, g_o, B, od, (int)HW, U->cfg.sigmoid_last_channel ? U->out_nchw : nullptr, r.st));
   // final 1x1 conv (the NHWC gradient has channel stride od, which may not be a multiple of 4: scalar staging)
   {
     const ConvLayer& L = U->final_conv;
-    if (U->have_grads || r.dry) {
+    if ((U->have_grads && !r.input_only) || r.dry) {
       ConvGeom g;
       if (geom_fwd_layer(L, B, 0, &g)) return -1;
       float* part = r.part_alloc(wgrad_ws_bytes(g));
@@ -1477,14 +1483,14 @@ static int backward_impl(Run& r, const float* grad_out_nchw, float* grad_x_nhwc)
     RUN(launch_act_bwd(U->e1, g_e1g, g_e1, nh, 1, r.st));
     if (conv_wgrad(r, U->emb1, U->cond_in, nullptr, g_e1)) return -1;
     g_h0 = g_h0p;
-    if (!r.dry) U->cond_grads_dirty = true;
+    if (!r.dry && !r.input_only) U->cond_grads_dirty = true;
   }
   if (conv_wgrad(r, U->init_conv, U->x_in, nullptr, g_h0)) return -1;
   if (grad_x_nhwc) {
     if (conv_dgrad(r, U->init_conv, g_h0, nullptr, grad_x_nhwc)) return -1;
   }
-  // ---- time path ----
-  if (U->have_grads || r.dry) {
+  // ---- time path ---- (t carries no gradient: the input-only pass has no use for dss)
+  if ((U->have_grads && !r.input_only) || r.dry) {
     const int nf = 4 * n + 2;
     ConvGeom g;
     if (geom_fwd_layer(U->lincat, B, 0, &g)) return -1;
@@ -1516,6 +1522,7 @@ static int backward_impl(Run& r, const float* grad_out_nchw, float* grad_x_nhwc)
     if (conv_wgrad(r, U->lin1, U->emb, nullptr, d_h1)) return -1;
   }
   // ---- every remaining queued fixed-order reduction (weight/bias/norm-parameter gradients) in one launch ----
+  if (r.input_only && !r.dry) return 0;     // (backward_input_body closes an open capture segment itself)
   if (flush_reductions(r, red_dev, &red_done, n_phases - 1, /*final_flush=*/true)) return -1;
   return 0;
 }
@@ -1788,6 +1795,24 @@ static int backward_body(pidm_unet* h, const float* grad_out_nchw, float* grad_x
   return 0;
 }
 
+// The input-gradient chain of backward_impl alone (Run::input_only): linear, on the caller's stream, no side stream, no events.
+// The arena layout is the full pass's (same plan, same keep_frames decision), so every data-path kernel sees the arguments it
+// would see there and grad_x is bit-identical.
+static int backward_input_body(pidm_unet* h, const float* grad_out_nchw, float* grad_x_nhwc, int B, void* workspace, size_t workspace_bytes,
+                               hipStream_t st, GraphCapture* cap) {
+  Run r;
+  r.cap = cap;
+  r.input_only = true;
+  if (setup_run(r, h, B, true, workspace, workspace_bytes, st, /*replay_plan=*/true)) return -1;
+  r.side_allowed = backward_eager(widest_level(h));
+  r.group_on = wgrad_group_on(B, h->cfg.image_size, r.side_allowed);   // nothing is queued; the frames are kept as the full pass keeps them
+  if (cap && cap_begin(r)) return -1;
+  if (backward_impl(r, grad_out_nchw, grad_x_nhwc)) return -1;
+  if (r.tmp.overflow() || r.defer.overflow()) return fail("unet_backward_input: internal arena overflow");
+  if (cap && cap->open && cap_end_segment(r, nullptr, false)) return -1;
+  return 0;
+}
+
 // closes a capture that an error left open, so that the stream can be used again
 static void cap_abort(pidm_unet* h, GraphCapture* cap) {
   if (cap->open) {
@@ -1923,6 +1948,50 @@ extern "C" int pidm_unet_backward(pidm_unet* h, const float* grad_out_nchw, floa
   if (rc == 0 && grad_x_nhwc && grad_x_nhwc != io.gx &&
       hipMemcpyAsync(grad_x_nhwc, io.gx, io.x_bytes, hipMemcpyDeviceToDevice, st) != hipSuccess)
     return fail("unet_backward: input-gradient copy failed");
+  return rc;
+}
+
+extern "C" int pidm_unet_backward_input(pidm_unet* h, const float* grad_out_nchw, float* grad_x_nhwc, int B, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+  if (!h || !grad_out_nchw || !grad_x_nhwc || !workspace) return fail("unet_backward_input: null argument");
+  if (B <= 0) return fail("unet_backward_input: B must be positive");
+  if (h->tape_B != B) return fail("unet_backward_input: no matching forward (tape holds B=%d)", h->tape_B);
+  if (h->tape_cond) return fail("unet_backward_input: the tape was recorded with a conditioning input (not supported)");
+  const hipStream_t st = as_stream(stream);
+  touch_arena(h, B, true, workspace, workspace_bytes);
+  const IoRegion io = io_region(h, B, reinterpret_cast<char*>(workspace) + packed_region_bytes(h));
+  if (grad_out_nchw != io.gout && hipMemcpyAsync(io.gout, grad_out_nchw, io.out_bytes, hipMemcpyDeviceToDevice, st) != hipSuccess)
+    return fail("unet_backward_input: gradient copy failed");
+  // a key (and a cache) of its own: the pass reads no gradient binding, no reduction table and no phase events
+  const uint64_t kw[7] = {0xB1, (uint64_t)B, (uint64_t)reinterpret_cast<uintptr_t>(workspace), (uint64_t)workspace_bytes, h->param_sig,
+                          env_signature(), h->fwd_key_hash};
+  const std::vector<uint64_t> key(kw, kw + 7);
+  const char* gb = knob("PIDM_GRAPH_BWD");
+  int rc = -1;
+  bool done = false;
+  if (graphs_enabled() && !(gb && !atoi(gb))) {
+    GraphEntry* e = graph_find(h, 2, key);
+    if (e) {
+      rc = graph_replay(e, st);
+      done = true;
+    } else if (graph_second_sighting(h, 2, key) && ensure_cap_stream(h)) {
+      e = graph_new_entry(h, 2, key);
+      GraphCapture cap;
+      cap.entry = e;
+      cap.user_st = st;
+      rc = backward_input_body(h, io.gout, io.gx, B, workspace, workspace_bytes, h->cap_stream, &cap);
+      cap_abort(h, &cap);
+      if (rc == 0 && !cap.failed) {
+        ++g_graph_captures;
+        done = true;
+      } else {
+        graph_drop_entry(h, 2, e);   // the eager path below redoes the whole pass
+      }
+    }
+  }
+  if (!done) rc = backward_input_body(h, io.gout, io.gx, B, workspace, workspace_bytes, st, nullptr);
+  if (rc == 0 && grad_x_nhwc != io.gx && hipMemcpyAsync(grad_x_nhwc, io.gx, io.x_bytes, hipMemcpyDeviceToDevice, st) != hipSuccess)
+    return fail("unet_backward_input: input-gradient copy failed");
   return rc;
 }
 

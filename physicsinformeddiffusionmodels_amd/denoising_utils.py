@@ -957,6 +957,83 @@ class DenoisingDiffusion(nn.Module):
             return (x_seq, interm_imgs), output[1]
         return x_seq, interm_imgs
 
+    def p_sample_loop_guided(self, shape, residual_func, obs, mask, zeta_obs=1.0, zeta_pde=0.0, guide_below=None,
+                             surpress_noise=True, replace_observed=False, keep_history=True):
+        """Conditional Darcy sampling by posterior guidance (an extension: the reference has no counterpart).
+
+        obs, mask: [B,2,P,P] or broadcastable [1,2,P,P]; channel 0 is p, channel 1 is K; the mask is 0/1.  K fully observed = the
+        forward problem, sparse p readings = the inverse problem, a few points of both = field completion.  At every step with
+        t < `guide_below` (default: every step) x_t is moved against the gradient, taken through the UNet to its input, of
+        Phi = zeta_obs sqrt(sum mask (x0_hat - obs)^2) + zeta_pde sqrt(sum r(x0_hat)^2) of the model's x0 estimate:
+        `input_gradient_pass` -> cotangent kernel -> `pull` -> x_{t-1} = c1 x0_hat + c2 x_t + sigma z - d Phi / d x_t
+        (four native calls; no weight gradient is computed and no gradient state of the model is touched).  Steps at or above
+        `guide_below` are plain `p_sample` arithmetic.  `replace_observed=True` writes `obs` into the masked entries of the final state.
+
+        zeta_obs / zeta_pde are user parameters.  Their defaults are PLACEHOLDERS: no trained checkpoint was available when this was
+        written, the right magnitudes depend on the model and the schedule, and nothing here claims sample quality.
+
+        Returns `((x_seq, interm), aux)` like `p_sample_loop(..., eval_residuals=True)`: aux['residual'] [B] = per-sample mean |r| of
+        the final state, aux['guidance'] [n_steps,B,2] = (L_obs, L_pde) of the x0 estimate per step in the order the steps are
+        taken (zeros for unguided steps), kept on the device - nothing is read back inside the loop."""
+        from ._engine import frozen_weights, input_gradient_pass
+        from ._lib import PidmError
+        if residual_func is None or getattr(residual_func, 'gov_eqs', None) != 'darcy':
+            raise PidmError("p_sample_loop_guided: Darcy only (residual_func must be a ResidualsDarcy)")
+        if getattr(residual_func, 'residual_grad_guidance', False) or getattr(residual_func, 'use_ddim_x0', False):
+            raise PidmError("p_sample_loop_guided: conditioning inputs / sample estimation are not supported")
+        net = residual_func.model
+        if getattr(net, 'self_condition', False):
+            raise PidmError("p_sample_loop_guided: self-conditioning models are not supported")
+        shape = tuple(shape)
+        if len(shape) != 4 or shape[1] != 2 or shape[2] != shape[3]:
+            raise PidmError(f"p_sample_loop_guided: shape must be (B,2,P,P), got {shape}")
+        B, _, P, _ = shape
+        for name, a in (('obs', obs), ('mask', mask)):
+            if not torch.is_tensor(a) or a.dim() != 4 or tuple(a.shape[1:]) != shape[1:] or a.shape[0] not in (1, B):
+                raise PidmError(f"p_sample_loop_guided: {name} must be [B,2,P,P] or [1,2,P,P] for shape {shape}, got "
+                                f"{tuple(a.shape) if torch.is_tensor(a) else type(a).__name__}")
+        dev = self.diff_dict['alphas'].device
+        obs_d = obs.detach().to(device=dev, dtype=torch.float32).expand(shape).contiguous()
+        mask_d = mask.detach().to(device=dev, dtype=torch.float32).expand(shape).contiguous()
+        guide_below = self.n_steps if guide_below is None else int(guide_below)
+        lib, ht = self.lib, self._host_tables
+        guidance = torch.zeros(self.n_steps, B, 2, dtype=torch.float32, device=dev)
+        cur_x = torch.randn(shape, device=dev)
+        x_seq = [cur_x.detach().cpu()] if keep_history else []
+        interm = [torch.zeros(shape)] if keep_history else []     # (as p_sample_loop(save_output=True): no estimate before the first step)
+        with torch.no_grad(), frozen_weights(net):
+            for k, i in enumerate(reversed(range(self.n_steps))):
+                tt = torch.full((B,), i, device=dev, dtype=torch.long)
+                xi = cur_x.contiguous()
+                c1, c2 = float(ht['posterior_mean_coef1'][i]), float(ht['posterior_mean_coef2'][i])
+                sigma = 0.0 if (surpress_noise and i == 0) else float(ht['betas'][i].sqrt())
+                out = torch.empty_like(xi)
+                if i < guide_below:
+                    x0p, pull = input_gradient_pass(net, xi, tt)
+                    v, _ = residual_func.guidance_cotangent(x0p, obs_d, mask_d, zeta_obs, zeta_pde, sums_out=guidance[k])
+                    g = pull(v)
+                    z = torch.randn_like(xi)
+                    lib.check(lib.pidm_psample_update_guided(ptr(x0p), ptr(xi), ptr(z), ptr(g), c1, c2, sigma, ptr(out), B, 2, P * P,
+                                                             stream_ptr(dev)), 'pidm_psample_update_guided')
+                else:
+                    x0p = net(image_to_b_xy_c(xi), tt).contiguous()
+                    z = torch.randn_like(xi)
+                    lib.check(lib.pidm_psample_update(ptr(x0p), ptr(xi), ptr(z), c1, c2, sigma, ptr(out), xi.numel(),
+                                                      stream_ptr(dev)), 'pidm_psample_update')
+                cur_x = out
+                if keep_history:
+                    x_seq.append(cur_x.cpu())
+                    interm.append(x0p.cpu())
+            if replace_observed:
+                cur_x = torch.where(mask_d != 0, obs_d, cur_x)
+                if keep_history:
+                    x_seq[-1] = cur_x.cpu()
+            residual = residual_func.residual_of(cur_x).abs().mean(dim=(1, 2))
+        if not keep_history:
+            x_seq.append(cur_x)
+            interm.append(x0p)
+        return (x_seq, interm), {'residual': residual, 'guidance': guidance}
+
     def ddim_sample_x0(self, xt, t, model, shape, reduced_n_steps, ddim_sampling_eta, gov_eqs=None, self_cond=None):
         """Sample estimation (src/denoising_utils.py:712-788).  The reference walks ddim_steps + 2 time levels from t down to 0
         but never updates `model_input`: every model call sees the same x_t, the value it returns is

@@ -156,6 +156,65 @@ class ResidualsDarcy:
         return _DarcyResidualGeneralFn.apply(x0_pred, self._f_s_flat, (sg.d_d0, sg.d_d1, sg.d_d00, sg.d_d11), self.periodic,
                                              1.0 if self.reverse_d1 else -1.0, self.lib)
 
+    def guidance_cotangent(self, x0_pred, obs, mask, zeta_obs, zeta_pde, sums_out=None):
+        """Posterior-guidance cotangent of an x0 estimate (csrc/k_guidance.hip).  x0_pred, obs, mask: [B,2,P,P] (mask 0/1).
+        Per sample Phi = zeta_obs sqrt(L_obs) + zeta_pde sqrt(L_pde) with L_obs = sum mask (x0_pred - obs)^2 and L_pde = sum r^2;
+        returns `(v, sums)`: v = dPhi/dx0_pred [B,2,P,P] and sums [B,2] = (L_obs, L_pde).  A term whose L is exactly 0 is omitted.
+        The second-order non-periodic configuration is one launch; the general stencil sets run residual -> scale -> adjoint ->
+        add on the device.  `sums_out`: a contiguous [B,2] fp32 tensor to write the sums into (no allocation, no copy)."""
+        if x0_pred.dim() != 4 or x0_pred.shape[1] != 2 or x0_pred.shape[-1] != x0_pred.shape[-2]:
+            raise PidmError(f'guidance_cotangent: x0_pred must be [B,2,P,P], got {tuple(x0_pred.shape)}')
+        if tuple(obs.shape) != tuple(x0_pred.shape) or tuple(mask.shape) != tuple(x0_pred.shape):
+            raise PidmError(f'guidance_cotangent: obs {tuple(obs.shape)} / mask {tuple(mask.shape)} must match x0_pred '
+                            f'{tuple(x0_pred.shape)}')
+        if self._lib is None and not x0_pred.is_cuda:
+            raise PidmError('ResidualsDarcy needs tensors on an MI355X: the gfx950 kernels have no CPU fallback')
+        lib, dev = self.lib, x0_pred.device
+        x = x0_pred.detach().contiguous().float()
+        y = obs.detach().to(dev).contiguous().float()
+        m = mask.detach().to(dev).contiguous().float()
+        B, _, P, _ = x.shape
+        if self._f_s_flat.device != dev:
+            self._f_s_flat = self._f_s_flat.to(dev)
+        v = torch.empty_like(x)
+        sums = sums_out if sums_out is not None else torch.empty(B, 2, dtype=torch.float32, device=dev)
+        if tuple(sums.shape) != (B, 2) or sums.dtype != torch.float32 or not sums.is_contiguous() or sums.device != dev:
+            raise PidmError('guidance_cotangent: sums_out must be a contiguous fp32 [B,2] tensor on the input device')
+        st = stream_ptr(dev)
+        # the one-launch kernel keeps a sample and its six adjoint operands in LDS (8 P^2 floats of the 160 KiB); larger fields take
+        # the composition below on the second-order residual kernels
+        if self.specialised and 8 * P * P * 4 <= 160 * 1024 - 256:
+            lib.check(lib.pidm_darcy_guidance_cotangent(ptr(x), ptr(y), ptr(m), ptr(self._f_s_flat), self.inv_h0, self.inv_h1,
+                                                        float(zeta_obs), float(zeta_pde), ptr(v), ptr(sums), B, P, st),
+                      'pidm_darcy_guidance_cotangent')
+            return v, sums
+        res = torch.empty(B, P * P, 3, dtype=torch.float32, device=dev)
+        gres = torch.empty_like(res)
+        adj = torch.empty_like(x)
+        if self.specialised:
+            fwd = lambda: lib.check(lib.pidm_darcy_residual_fwd(ptr(x), ptr(self._f_s_flat), self.inv_h0, self.inv_h1, ptr(res), B, P, st),
+                                    'pidm_darcy_residual_fwd')
+            bwd = lambda: lib.check(lib.pidm_darcy_residual_bwd(ptr(x), ptr(gres), self.inv_h0, self.inv_h1, ptr(adj), B, P, st),
+                                    'pidm_darcy_residual_bwd')
+        else:
+            sg = self.grads.stencil_gradients
+            need = max(getattr(sg, k).min_size() for k in ('d_d0', 'd_d1', 'd_d00', 'd_d11'))
+            if P < need:
+                raise ValueError(f'a {P} x {P} field does not fit the fd_acc={self.fd_acc} stencils (>= {need})')
+            ops, keep = _ops_array((sg.d_d0, sg.d_d1, sg.d_d00, sg.d_d11), dev)
+            bc1_sign = 1.0 if self.reverse_d1 else -1.0
+            ws = torch.empty(lib.pidm_darcy_general_ws(B, P), dtype=torch.uint8, device=dev)
+            fwd = lambda: lib.check(lib.pidm_darcy_residual_general_fwd(ptr(x), ptr(self._f_s_flat), ops, int(self.periodic), bc1_sign,
+                                                                        ptr(res), ptr(ws), B, P, st), 'pidm_darcy_residual_general_fwd')
+            bwd = lambda: lib.check(lib.pidm_darcy_residual_general_bwd(ptr(x), ptr(gres), ops, int(self.periodic), bc1_sign, ptr(adj),
+                                                                        ptr(ws), B, P, st), 'pidm_darcy_residual_general_bwd')
+        fwd()
+        lib.check(lib.pidm_guidance_scale_general(ptr(x), ptr(y), ptr(m), ptr(res), float(zeta_obs), float(zeta_pde), ptr(gres),
+                                                  ptr(v), ptr(sums), B, P, st), 'pidm_guidance_scale_general')
+        bwd()
+        lib.check(lib.pidm_guidance_add(ptr(v), ptr(adj), v.numel(), st), 'pidm_guidance_add')
+        return v, sums
+
     def compute_residual(self, input, reduce='none', return_model_out=False, return_optimizer=False,
                          return_inequality=False, sample=False, ddim_func=None, pass_through=False):
         if pass_through:

@@ -304,3 +304,10 @@ class Unet3D(nn.Module):
             return logits
         null_logits = self.forward(*args, null_cond_prob=1., **kwargs)
         return null_logits + (logits - null_logits) * guidance_scale
+
+
+def input_gradient_pass(model, x, t, lib=None, cond=None):
+    """`(x0_pred, pull)`: one UNet evaluation and the pull-back of a cotangent of its output to its input, with no weight gradient
+    computed and no gradient state of `model` touched (see `_engine.input_gradient_pass`)."""
+    from ._engine import input_gradient_pass as impl
+    return impl(model, x, t, lib=lib, cond=cond)

@@ -1,0 +1,129 @@
+"""One guided sampler step at dim 32, 64 x 64, three ways in ONE process on one GPU (ms per step, device events):
+  (a) inference forward only (an unguided step's UNet cost),
+  (b) training-mode forward + pidm_unet_backward with an input gradient - how an input gradient was obtained before
+      pidm_unet_backward_input existed (weight gradients computed and thrown away),
+  (c) input_gradient_pass + cotangent kernel + pull + guided update kernel - the step of p_sample_loop_guided;
+      (c-unet) is its UNet part alone (input_gradient_pass + pull), the like-for-like counterpart of (b).
+The legs alternate inside every round; the median over the rounds is reported, with the kernels per step from
+pidm_debug_launch_counts (enqueued launch by launch + inside replayed graphs).  Usage: bench_guided.py [--out FILE] [BATCH ...]"""
+import ctypes as C
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from oracle import pidm_oracle as O  # noqa: E402
+from physicsinformeddiffusionmodels_amd._engine import frozen_weights  # noqa: E402
+from physicsinformeddiffusionmodels_amd._lib import get_lib, ptr, stream_ptr  # noqa: E402
+from physicsinformeddiffusionmodels_amd.residuals_darcy import ResidualsDarcy  # noqa: E402
+from physicsinformeddiffusionmodels_amd.unet_model import Unet3D, input_gradient_pass  # noqa: E402
+
+
+def kernels(L):
+    a = (C.c_longlong * 4)()
+    L.check(L.pidm_debug_launch_counts(a))
+    return a[0] + a[2]
+
+
+def engine_clock(L, dev, B):
+    """the shader clock under load, as bench.py's roofline leg measures it (stamps inside a convolution kernel)"""
+    try:
+        from bench import rs_clock_probe
+        probe = rs_clock_probe(L, dev, B) or {}
+        ghz = probe.get("shader_clock_ghz")
+        return f"{ghz:.2f} GHz" if ghz else "not measured"
+    except Exception:
+        return "not measured"
+
+
+def main():
+    args = sys.argv[1:]
+    out_path = None
+    if "--out" in args:
+        i = args.index("--out")
+        out_path = args[i + 1]
+        del args[i:i + 2]
+    batches = [int(a) for a in args] or [64, 1024]
+    assert torch.cuda.is_available(), "bench_guided.py measures on an MI355X"
+    L, dev, dim, P = get_lib(), torch.device("cuda:0"), 32, 64
+    prop = torch.cuda.get_device_properties(0)
+    lines = [f"guided step, dim {dim}, {P} x {P}; device: {prop.name}, {prop.multi_processor_count} CUs, "
+             f"shader clock under load {engine_clock(L, dev, 64)}; ms per step = median of rounds (min .. max)"]
+    m = Unet3D(dim=dim, channels=2)
+    m.load_state_dict(O.fill_state_dict(m.state_dict()))
+    m = m.to(dev)
+    res = ResidualsDarcy(model=m, fd_acc=2, pixels_per_dim=P, pixels_at_boundary=True, reverse_d1=True, device=dev)
+    rounds, inner, warm = 7, 5, 4
+    for B in batches:
+        g = torch.Generator().manual_seed(B)
+        x = torch.randn(B, 2, P, P, generator=g).to(dev)
+        z = torch.randn(B, 2, P, P, generator=g).to(dev)
+        w = torch.randn(B, 2, P, P, generator=g).to(dev)
+        obs = torch.randn(B, 2, P, P, generator=g).to(dev)
+        obs[:, 1] = torch.exp(0.5 * obs[:, 1])
+        mask = (torch.rand(B, 2, P, P, generator=g) < 0.1).float().to(dev)
+        t = torch.full((B,), 50, dtype=torch.long, device=dev)
+        x_nhwc = x.permute(0, 2, 3, 1).reshape(B, P * P, 2).contiguous()
+        out = torch.empty_like(x)
+
+        def leg_a():
+            with torch.no_grad():
+                m(x_nhwc, t)
+
+        def leg_b():
+            xr = x_nhwc.detach().requires_grad_(True)
+            m(xr, t).backward(w)
+            for p in m.parameters():
+                p.grad = None
+
+        def leg_c_unet():
+            with torch.no_grad():
+                x0p, pull = input_gradient_pass(m, x_nhwc, t)
+                pull(w)
+
+        def leg_c():
+            with torch.no_grad():
+                x0p, pull = input_gradient_pass(m, x_nhwc, t)
+                v, _ = res.guidance_cotangent(x0p, obs, mask, 1.0, 1e-3)
+                gr = pull(v)
+                L.check(L.pidm_psample_update_guided(ptr(x0p), ptr(x), ptr(z), ptr(gr), 0.3, 0.7, 0.05, ptr(out), B, 2, P * P, stream_ptr(dev)))
+
+        legs = [("a  inference forward", leg_a), ("b  training forward + full backward", leg_b),
+                ("c-unet  input_gradient_pass + pull", leg_c_unet), ("c  guided step (4 native calls)", leg_c)]
+        times = {k: [] for k, _ in legs}
+        count = {}
+        with frozen_weights(m):
+            for k, fn in legs:
+                for _ in range(warm):       # eager, capture, replay, replay
+                    fn()
+                torch.cuda.synchronize()
+                k0 = kernels(L)
+                fn()
+                count[k] = kernels(L) - k0
+            for _ in range(rounds):
+                for k, fn in legs:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(inner):
+                        fn()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    times[k].append(e0.elapsed_time(e1) / inner)
+        lines.append(f"batch {B}:")
+        for k, _ in legs:
+            v = times[k]
+            lines.append(f"  ({k:42s}) {statistics.median(v):9.3f} ms  ({min(v):.3f} .. {max(v):.3f})  {count[k]:4d} kernels / step")
+        b_, c_ = statistics.median(times[legs[1][0]]), statistics.median(times[legs[2][0]])
+        lines.append(f"  c-unet / b = {c_ / b_:.3f}")
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write(text)
+
+
+if __name__ == "__main__":
+    main()
