@@ -250,7 +250,8 @@ int pidm_darcy_gen(const double* basis, const double* z, int q, const double* K_
  *                   (src/darcy_data_generation.py:129-142, every FinDiff(..., acc=acc)): rows i < acc/2 forward, rows
  *                   i > P-1-acc/2 backward, the others central; central and one-sided first-derivative stencils have acc+1 taps,
  *                   one-sided second-derivative stencils acc+2.  K_0 and K_1 come from the same operators.  Arguments as
- *                   pidm_darcy_gen, plus:
+ *                   pidm_darcy_gen, plus (this entry and pidm_darcy_gen_periodic run one solver, csrc/k_darcy_gen_cgls.h, with
+ *                   the 1-D operators of csrc/k_darcy_gen_acc.hip / csrc/k_darcy_gen_per.hip):
  *                   launch protocol - one call runs at most iters_this_launch (>= 1) CGLS iterations per sample that is not done
  *                   and returns; the caller repeats the call (first_launch = 0, every other argument unchanged) until done[b] != 0
  *                   for every b.  first_launch != 0 initialises `state` (whatever it held).  A sample is finished when it

@@ -214,6 +214,13 @@ def _check_converged(relres, rtol, labels):
         raise PidmError(f"darcy solve did not converge (||S A^T r|| / ||S A^T b|| > {rtol:g}) for sample(s) {bad}: raise max_iter")
 
 
+def _outputs(B, P, device):
+    """K, p [B, P^2], res [B], iters [B] (int32), relres [B]: what either entry writes"""
+    f64 = dict(dtype=torch.float64, device=device)
+    return (torch.empty(B, P * P, **f64), torch.empty(B, P * P, **f64), torch.empty(B, **f64),
+            torch.empty(B, dtype=torch.int32, device=device), torch.empty(B, **f64))
+
+
 def _launch(lib, device, prob, *, basis=None, z=None, K_in=None, B, max_iter, rtol, iters_per_launch=None, resumable=False,
             stats=None):
     if prob.acc != 2 or resumable or prob.periodic:
@@ -221,11 +228,7 @@ def _launch(lib, device, prob, *, basis=None, z=None, K_in=None, B, max_iter, rt
                            iters_per_launch=iters_per_launch, stats=stats)
     P = prob.P
     f_s, int_w = prob.on(device)
-    K = torch.empty(B, P * P, dtype=torch.float64, device=device)
-    p = torch.empty(B, P * P, dtype=torch.float64, device=device)
-    res = torch.empty(B, dtype=torch.float64, device=device)
-    iters = torch.empty(B, dtype=torch.int32, device=device)
-    relres = torch.empty(B, dtype=torch.float64, device=device)
+    K, p, res, iters, relres = _outputs(B, P, device)
     q = 0 if z is None else z.shape[1]
     lib.check(lib.pidm_darcy_gen(ptr(basis), ptr(z), q, ptr(K_in), P, prob.d0, prob.d1, prob.bc_sign, ptr(int_w), ptr(f_s),
                                  int(max_iter), float(rtol), ptr(K), ptr(p), ptr(res), ptr(iters), ptr(relres), B,
@@ -253,11 +256,7 @@ def _launch_acc(lib, device, prob, *, basis=None, z=None, K_in=None, B, max_iter
         cus = torch.cuda.get_device_properties(device).multi_processor_count
         iters_per_launch = max(1, iters_per_launch // -(-B // cus))
     iters_per_launch = min(iters_per_launch, 2 ** 31 - 1)
-    K = torch.empty(B, P * P, dtype=torch.float64, device=device)
-    p = torch.empty(B, P * P, dtype=torch.float64, device=device)
-    res = torch.empty(B, dtype=torch.float64, device=device)
-    iters = torch.empty(B, dtype=torch.int32, device=device)
-    relres = torch.empty(B, dtype=torch.float64, device=device)
+    K, p, res, iters, relres = _outputs(B, P, device)
     done = torch.zeros(B, dtype=torch.int32, device=device)
     state = torch.empty(max(1, lib.pidm_darcy_gen_acc_state_bytes(P, B) // 8), dtype=torch.float64, device=device)
     q = 0 if z is None else z.shape[1]

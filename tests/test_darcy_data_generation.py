@@ -1,5 +1,6 @@
 """Darcy training-data generation (csrc/k_darcy_gen.hip, physicsinformeddiffusionmodels_amd/darcy_data_generation.py) against a
 dense float64 least-squares oracle, the reference generator's golden samples (g25) and the engine's own training residual."""
+import functools
 import os
 
 import numpy as np
@@ -8,8 +9,8 @@ import torch
 
 from physicsinformeddiffusionmodels_amd import darcy_data_generation as D
 from physicsinformeddiffusionmodels_amd._lib import PidmError
-
-TOL = 1e-6
+from tests import darcy_gen_ref as R
+from tests.darcy_gen_ref import CASES, TOL, emu_or_gpu as _emu_or_gpu
 
 
 def _d(P, h, order):
@@ -25,56 +26,19 @@ def _d(P, h, order):
     return M / h ** order
 
 
-def dense_lstsq(K, P, pab, rev):
-    """The reference system (src/darcy_data_generation.py:135-163, same row order) assembled densely and solved by lstsq."""
-    pr = D.DarcyProblem(P, pab, rev)
-    eye = np.eye(P)
-    A0, A00 = np.kron(_d(P, pr.d0, 1), eye), np.kron(_d(P, pr.d0, 2), eye)
-    A1, A11 = np.kron(eye, _d(P, pr.d1, 1)), np.kron(eye, _d(P, pr.d1, 2))
-    k = K.reshape(-1)
-    k0, k1 = A0 @ k, A1 @ k
-    A = -k[:, None] * A00 - k0[:, None] * A0 - k[:, None] * A11 - k1[:, None] * A1
-    xmin, xmax, ymin, ymax = D.create_boundary_idcs((P, P))
-    s = 1. if rev else -1.
-    Abi = np.concatenate([A, -A0[xmin], A0[xmax], s * A1[ymin], -s * A1[ymax], pr.int_w.reshape(1, -1)])
-    b = np.concatenate([pr.f_s, np.zeros(4 * P + 1)])
-    p = np.linalg.lstsq(Abi, b, rcond=None)[0]
-    return p, np.abs(Abi @ p - b).mean()
-
-
-def _field(P, pab, seed):
-    basis = D.kle_basis(P, 0.1, min(64, P * P), pab)
-    return np.exp(basis.T @ D.z_of_seed(seed, basis.shape[0])).reshape(P, P)
-
-
-def _emu_or_gpu(backend):
-    L, dev = backend
-    return (L if dev.type == "cpu" else None), dev
-
-
-CASES = [(True, True), (True, False), (False, True), (False, False)]
+_dense_case = functools.partial(R.dense_case, lambda P, h, order, acc: _d(P, h, order), "none")   # (this file's second-order rows)
 
 
 @pytest.mark.parametrize("P", [8, 16])
 @pytest.mark.parametrize("pab,rev", CASES)
 def test_solve_matches_dense_lstsq(backend, P, pab, rev):
-    _dense_case(*_emu_or_gpu(backend), P, pab, rev)
+    _dense_case(*_emu_or_gpu(backend), P, pab, rev, 2)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("pab,rev", CASES)
 def test_solve_matches_dense_lstsq_p32(pab, rev):
-    _dense_case(None, torch.device("cuda:0"), 32, pab, rev)
-
-
-def _dense_case(lib, dev, P, pab, rev):
-    K = np.stack([_field(P, pab, 11 + P), _field(P, pab, 977)])
-    p, res = D.solve_darcy_pressure(torch.from_numpy(K).to(dev), pab, rev, lib=lib)
-    p, res = p.cpu().numpy(), res.cpu().numpy()
-    for s in range(2):
-        pref, rref = dense_lstsq(K[s], P, pab, rev)
-        assert np.abs(p[s].reshape(-1) - pref).max() <= TOL * np.abs(pref).max()
-        assert abs(res[s] - rref) <= TOL * rref
+    _dense_case(None, torch.device("cuda:0"), 32, pab, rev, 2)
 
 
 def test_kle_synthesis_matches_numpy(backend):

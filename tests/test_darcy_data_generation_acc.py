@@ -12,11 +12,11 @@ import torch
 from physicsinformeddiffusionmodels_amd import darcy_data_generation as D
 from physicsinformeddiffusionmodels_amd import grad_utils as G
 from physicsinformeddiffusionmodels_amd._lib import PidmError, ptr, stream_ptr
+from tests import darcy_gen_ref as R
+from tests.darcy_gen_ref import CASES, TOL, emu_or_gpu as _emu_or_gpu, field as _field
 
-# the project's figure for this solve (tests/test_darcy_data_generation.py).  A NumPy CGLS with the kernel's algorithm (column
+# TOL: the project's figure for this solve (tests/darcy_gen_ref.py).  A NumPy CGLS with the kernel's algorithm (column
 # scaling, rtol 1e-12, deflation) stays at or below 3.4e-9 on p and 1.4e-9 on the residual for every case here.
-TOL = 1e-6
-CASES = [(True, True), (True, False), (False, True), (False, False)]
 
 
 def _d(P, h, order, acc):
@@ -29,58 +29,7 @@ def _d(P, h, order, acc):
     return M / h ** order
 
 
-@functools.lru_cache(maxsize=None)
-def _system(P, pab, rev, acc, seed):
-    """(K, A_bc_int, b) of the reference system (src/darcy_data_generation.py:135-163, same row order) at order acc."""
-    K = _field(P, pab, seed)
-    pr = D.DarcyProblem(P, pab, rev, acc=acc)
-    eye = np.eye(P)
-    A0, A00 = np.kron(_d(P, pr.d0, 1, acc), eye), np.kron(_d(P, pr.d0, 2, acc), eye)
-    A1, A11 = np.kron(eye, _d(P, pr.d1, 1, acc)), np.kron(eye, _d(P, pr.d1, 2, acc))
-    k = K.reshape(-1)
-    k0, k1 = A0 @ k, A1 @ k
-    A = -k[:, None] * A00 - k0[:, None] * A0 - k[:, None] * A11 - k1[:, None] * A1
-    xmin, xmax, ymin, ymax = D.create_boundary_idcs((P, P))
-    s = 1. if rev else -1.
-    Abi = np.concatenate([A, -A0[xmin], A0[xmax], s * A1[ymin], -s * A1[ymax], pr.int_w.reshape(1, -1)])
-    b = np.concatenate([pr.f_s, np.zeros(4 * P + 1)])
-    return K, Abi, b
-
-
-@functools.lru_cache(maxsize=None)
-def dense_lstsq(P, pab, rev, acc, seed):
-    """(K, p, mean |row residual|) by lstsq; computed once per case and shared (callers do not modify the arrays)."""
-    K, Abi, b = _system(P, pab, rev, acc, seed)
-    p = np.linalg.lstsq(Abi, b, rcond=None)[0]
-    return K, p, np.abs(Abi @ p - b).mean()
-
-
-@functools.lru_cache(maxsize=None)
-def _basis(P, pab):
-    return D.kle_basis(P, 0.1, min(64, P * P), pab)
-
-
-def _field(P, pab, seed):
-    basis = _basis(P, pab)
-    return np.exp(basis.T @ D.z_of_seed(seed, basis.shape[0])).reshape(P, P)
-
-
-def _emu_or_gpu(backend):
-    L, dev = backend
-    return (L if dev.type == "cpu" else None), dev
-
-
-def _dense_case(lib, dev, P, pab, rev, acc):
-    seeds = (11 + P, 977)
-    ref = [dense_lstsq(P, pab, rev, acc, s) for s in seeds]
-    K = np.stack([r[0] for r in ref])
-    p, res, iters = D.solve_darcy_pressure(torch.from_numpy(K).to(dev), pab, rev, lib=lib, acc=acc, return_iters=True)
-    p, res = p.cpu().numpy(), res.cpu().numpy()
-    for s, (_, pref, rref) in enumerate(ref):
-        ep, er = np.abs(p[s].reshape(-1) - pref).max() / np.abs(pref).max(), abs(res[s] - rref) / rref
-        print(f"acc {acc} P {P} pab {pab} rev {rev} seed {seeds[s]}: iters {int(iters[s])} err p {ep:.3e} err res {er:.3e}")
-        assert ep <= TOL
-        assert er <= TOL
+dense_lstsq, _dense_case = functools.partial(R.dense_lstsq, _d, "none"), functools.partial(R.dense_case, _d, "none")
 
 
 # ---- 1. dense oracle ------------------------------------------------------------------------------------------------------------
@@ -156,12 +105,19 @@ def test_resumable_acc2_matches_second_order_kernel(backend, P):
         assert abs(float(r[s]) - float(rref[s])) <= TOL * float(rref[s])
 
 
+@pytest.mark.parametrize("pab,rev", CASES)
+def test_resumable_acc2_matches_dense_lstsq(backend, pab, rev):
+    """The classed instantiation of order 2 against the dense oracle at the smallest grid the entry accepts (the edge classes touch
+    the central band), cut into launches of 300 iterations."""
+    _dense_case(*_emu_or_gpu(backend), 8, pab, rev, 2, resumable=True, iters_per_launch=300)
+
+
 # ---- 5. batch invariance ----------------------------------------------------------------------------------------------------------------
 
 def test_batch_invariance(backend):
     lib, dev = _emu_or_gpu(backend)
     P = 10
-    basis = _basis(P, True)
+    basis = R.basis(P, True)
     seeds = list(range(100, 113))
     Kb, pb, rb, _ = D.generate_darcy_batch(seeds, P, basis=basis, device=dev, lib=lib, acc=4)
     K1, p1, r1, _ = D.generate_darcy_batch([seeds[7]], P, basis=basis, device=dev, lib=lib, acc=4)
@@ -217,7 +173,7 @@ def test_errors(backend):
         D.solve_darcy_pressure(one(65), lib=lib, acc=4)
     P = 10
     with pytest.raises(PidmError, match=r"did not converge.*#0 \(seed 1\).*#1 \(seed 2\)"):
-        D.generate_darcy_batch([1, 2], P, basis=_basis(P, True), device=dev, lib=lib, acc=4, max_iter=3)
+        D.generate_darcy_batch([1, 2], P, basis=R.basis(P, True), device=dev, lib=lib, acc=4, max_iter=3)
     with pytest.raises(PidmError, match="iters_per_launch"):
         D.solve_darcy_pressure(one(P), lib=lib, acc=4, iters_per_launch=0)
     # the native entry point itself rejects what the Python layer would have caught

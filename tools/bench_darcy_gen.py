@@ -2,8 +2,8 @@
 (min / median / max) at P = 64 for batches of 256 and 1024, and at P = 32.  The KLE basis (host eigh) is computed once per P
 and not timed.  --acc 4 / 6 (csrc/k_darcy_gen_acc.hip) and --resumable (acc 2 through the same entry) also report the number of
 launches and the longest single launch (launch + read-back of the done flags).  --bcs periodic (csrc/k_darcy_gen_per.hip) solves
-the periodic system on fields of the periodic KLE basis, through the same launches.  Results go to stdout; DESIGN.md / profiles/ keep the
-recorded numbers.
+the periodic system on fields of the periodic KLE basis, through the same launches (both files instantiate the solver body of
+csrc/k_darcy_gen_cgls.h).  Results go to stdout; DESIGN.md / profiles/ keep the recorded numbers.
 
     python tools/bench_darcy_gen.py [--cases 64:256,64:1024,32:256] [--acc 4] [--iters-per-launch N] [--resumable] [--bcs periodic]
 """
