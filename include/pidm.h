@@ -448,6 +448,21 @@ int pidm_conv_forward(const pidm_conv_desc* d, const float* src0, const float* s
  * written, 0 when the shape has no statistics epilogue (then only `out` is written), < 0 on error. */
 int pidm_conv_forward_gn_partials(const pidm_conv_desc* d, const float* src0, const float* src1, const float* w_packed,
                                   const float* bias, float* out, int groups, double* partial, void* stream);
+/* One half of a ResnetBlock as the engine runs it (Block: proj -> norm -> FiLM -> SiLU, src/unet_model.py:227-241), 3x3 / stride 1:
+ * a = conv(src) + bias, y = SiLU((GroupNorm(a) * gamma + beta) * (1 + scale) + shift) [+ res], stats[B][groups][2] = (mean, rstd);
+ * scale | shift = ss[b][0..2 Cout) + ssb (ss NULL: none), res laid out like y (NULL: none).  Where a workgroup's tile holds whole
+ * images (16 x 16 and 8 x 8 at engine batch sizes) the convolution finishes the GroupNorm itself: returns 1; else 0 (separate
+ * GroupNorm launches), < 0 on error.  PIDM_NO_GN_FUSED=1: always separate.  ws: B*H*W/32*Cout*2 doubles + B*2*Cout floats. */
+int pidm_conv_gn_forward(const pidm_conv_desc* d, const float* src0, const float* src1, const float* w_packed, const float* bias,
+                         int groups, const float* gamma, const float* beta, const float* ss, const float* ssb, int ldss,
+                         const float* res, float* a, float* y, float* stats, void* ws, void* stream);
+/* ... and its backward: dy = input gradient of the convolution d (the block's NEXT convolution; weights packed with mode 1) from
+ * g_c, dx = gradient wrt x of y = SiLU(FiLM(GroupNorm(x))) at dy (x, stats as the forward left them), dgb[B][2][C] = per-image
+ * dgamma | dbeta rows, dss[B][ldss] = FiLM gradient rows (ss NULL: untouched).  Returns 1 when the convolution did all of it (dy is
+ * then not written), 0 for separate launches, < 0 on error.  ws as above. */
+int pidm_conv_dgrad_gn_backward(const pidm_conv_desc* d, const float* g_c, const float* w_packed_dgrad, const float* x,
+                                const float* stats, int groups, const float* gamma, const float* beta, const float* ss,
+                                const float* ssb, int ldss, float* dss, float* dgb, float* dy, float* dx, void* ws, void* stream);
 /* adjoint wrt the input: dx[B,Hi,Wi,Cin] (+ residual) from dy[B,Ho,Wo,Cout]; weights packed with mode 1 */
 size_t pidm_conv_dgrad_packed_weight_floats(const pidm_conv_desc* d);
 int pidm_conv_dgrad(const pidm_conv_desc* d, const float* dy, int ld_dy, const float* w_packed_dgrad,

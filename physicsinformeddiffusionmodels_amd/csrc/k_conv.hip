@@ -130,11 +130,17 @@ __device__ __forceinline__ void split_cursor_next(SplitCursor& c, int NCH, int C
 // the strided one) as 4 output-parity problems of 2x2 taps (ConvGeom::nz = 4: work item = (parity, n-tile, m-tile), the epilogue
 // scatters with an output stride of 2).  Both keep the 3x3 halo-tile layout (one halo row / column on either side; the tap
 // offsets depend on the phase / parity) and run 4 taps = 24 MFMAs per wave and stage.
-template <int NW, int MODE>
+// FZ (MODE 0 only) = 1 / 2: the epilogue also FINISHES the GroupNorm that follows the convolution in a ResnetBlock (1: forward,
+// ConvGeom::gf_out) or its backward (2: the launch is conv 2's input gradient, ConvGeom::bf_dx) - launched where the workgroup's tile
+// holds whole images and its 32 channels whole groups (16 x 16 and 8 x 8 levels), so that the statistics never leave the workgroup:
+// the waves leave their sums in LDS rows behind the two buffers, meet at the stage's barrier and normalise the tile they still hold
+// in registers (k_conv_epilogue.h: pidm_fz_*).  Kernels of their own: FZ = 0 compiles to what it was without them.
+template <int NW, int MODE, int FZ = 0>
 __global__ void __launch_bounds__(64 * NW) conv3x3_split_kernel(ConvGeom g, const float* __restrict__ src0, const float* __restrict__ src1,
                                                             const unsigned short* __restrict__ ws, const float* __restrict__ bias,
                                                             const float* __restrict__ residual, float* __restrict__ out, int n_items,
                                                             int items_per_wg, int trace) {
+  static_assert(FZ == 0 || MODE == 0, "the GroupNorm-finishing epilogues (FZ = 1 forward, 2 backward) belong to the 3x3 / stride-1 form");
   constexpr int RB = kSplitRow, T = (MODE == 0) ? 9 : 4, NT = 64 * NW;   // NW waves: 8 (256-pixel tile, two waves per SIMD) or 4 (128 pixels)
   constexpr int NB = ((MODE == 0) ? 32 : 16) / NW;          // 1 KB pieces of the weight slab per wave (31.5 KB / 14 KB: the tail spills)
   constexpr int NBT = (MODE == 0) ? 4 : 2;                  // taps the slab copies are spread over
@@ -271,7 +277,9 @@ __global__ void __launch_bounds__(64 * NW) conv3x3_split_kernel(ConvGeom g, cons
   for (int r = 0; r < 16; ++r) { acc[r] = 0.f; accb[r] = 0.f; }
   // PIDM_STREAM_TRACE=1: cycle stamps of workgroup 0, waves 0 and 4 (one SIMD): [wave][stage < 32][top, taps done, epilogue done, past barrier]
   const int tr_base = (trace && blockIdx.x == 0 && lane == 0 && (wave & 3) == 0) ? (wave >> 2) * 128 : -1;
+  double* const fz_rows = reinterpret_cast<double*>(smem + 2 * (size_t)bufsz);   // behind the two buffers (launched with ConvGeom::gf_out / bf_dx only)
   for (int s = 0; s < nst; ++s) {
+    bool stage_synced = false;
     if (tr_base >= 0 && s < 32) g_stream_trace[tr_base + 4 * s + 0] = clock64();
     const char* wn1 = l_wn;        // weight slab of stage s+1 (copied during this stage)
     split_cursor_next<MODE>(lc, NCH, CCH, g.tiles_m, tpi, ntn);
@@ -358,9 +366,14 @@ __global__ void __launch_bounds__(64 * NW) conv3x3_split_kernel(ConvGeom g, cons
       const int p0 = wave * 32;
       const int tx0 = p0 & (g.Wv - 1), ty0 = (p0 >> g.wsh) & (g.TH - 1), img0 = p0 >> (g.wsh + g.tsh);
       const int b = b0 + img0;
+      // GroupNorm finished in the workgroup (ConvGeom::gf_out / bf_dx, k_conv_epilogue.h): the tile's values stay in v / fzk
+      constexpr bool fz_fwd = FZ == 1, fz_bwd = FZ == 2;
+      const bool fz_live = b < g.B && img0 < g.NI;
+      const int fz_pin = (vy0 + ty0) * g.Wv + tx0;
+      float v[16];
+      FzBwdKeep fzk;
       if (b < g.B && img0 < g.NI) {        // wave-uniform
         const int pin = (vy0 + ty0) * g.Wv + tx0;
-        float v[16];
         float gs1 = 0.f, gs2 = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -368,11 +381,14 @@ __global__ void __launch_bounds__(64 * NW) conv3x3_split_kernel(ConvGeom g, cons
           gs1 += v[r];
           gs2 += v[r] * v[r];
         }
-        if (g.gn_part) PIDM_GN_PARTIAL(gs1, gs2, b, pin, c)
-        if (g.bn_part) {
+        if (FZ == 0 && g.gn_part) PIDM_GN_PARTIAL(gs1, gs2, b, pin, c)
+        if (fz_fwd) pidm_fz_fwd_put(g, fz_rows, wave, gs1, gs2, half, l31);
+        if (FZ == 0 && g.bn_part) {
           const float* xrow = g.bn_x + ((size_t)b * g.Ho * g.Wo + pin) * g.Cout + c;
           PIDM_BN_PARTIAL(acc, bv, b, pin, c, xrow, g.Cout, (g.bn_res && residual != nullptr), residual + ((size_t)b * g.Ho * g.Wo + pin) * g.ldr + c, g.ldr)
         }
+        if (fz_bwd) pidm_fz_bwd_put(g, fz_rows, wave, acc, bv, b, c, g.bn_x + ((size_t)b * g.Ho * g.Wo + pin) * g.Cout + c, half, l31, fzk);
+        if (!fz_bwd) {                     // (the fused backward writes the GroupNorm's input gradient instead of this tensor)
         const bool odd1 = (l31 & 1) != 0, odd2 = (l31 & 2) != 0;
         const size_t opix = (size_t)b * g.sob + (size_t)pin * g.sox + n0 + 4 * (l31 >> 2);
         const size_t rpix = ((size_t)b * g.Ho * g.Wo + pin) * g.ldr + n0 + 4 * (l31 >> 2);
@@ -405,12 +421,28 @@ __global__ void __launch_bounds__(64 * NW) conv3x3_split_kernel(ConvGeom g, cons
           *reinterpret_cast<f32x4*>(out + opix + (size_t)prow * g.sox) = o;
           }
         }
+        }
       }
       for (int r = 0; r < 16; ++r) { acc[r] = 0.f; accb[r] = 0.f; }
+      if (fz_fwd || fz_bwd) {
+        // this stage's barrier, taken here (every wave of the workgroup takes this branch together: it depends on kernel arguments
+        // and the stage only), so that what crosses it lives in this block and not around the stage loop; behind it the sums of all
+        // waves are in LDS.  The rows are written again NCH >= 2 stages on, behind the next barrier at the earliest.
+        if (tr_base >= 0 && s < 32) g_stream_trace[tr_base + 4 * s + 2] = clock64();
+        split_cursor_next<MODE>(cs, NCH, CCH, g.tiles_m, tpi, ntn);
+        __syncthreads();             // buffer (s+1)&1 complete, buffer s&1 free
+        stage_synced = true;
+        if (fz_live) {
+          if (fz_fwd) pidm_fz_fwd_finish(g, fz_rows, wave, b, fz_pin, n0, v, half, l31);
+          else pidm_fz_bwd_finish(g, fz_rows, wave, b, fz_pin, n0, fzk, half, l31);
+        }
+      }
     }
+    if (!stage_synced) {
     if (tr_base >= 0 && s < 32) g_stream_trace[tr_base + 4 * s + 2] = clock64();
     split_cursor_next<MODE>(cs, NCH, CCH, g.tiles_m, tpi, ntn);
     __syncthreads();               // buffer (s+1)&1 complete, buffer s&1 free
+    }
     if (tr_base >= 0 && s < 32) g_stream_trace[tr_base + 4 * s + 3] = clock64();
     char* tswap = bufc; bufc = bufn; bufn = tswap;
   }
@@ -431,8 +463,10 @@ __global__ void __launch_bounds__(64 * NW) conv3x3_split_kernel(ConvGeom g, cons
 // and fetch the activations of stage s+2.  The producers' VALU and LDS-write work runs beside the consumers' MFMAs on every SIMD
 // for the whole stage (~900 of ~3850 cycles).  Same buffers, same barrier per stage, same arithmetic in the same order: results
 // are bit-identical to conv3x3_split_kernel.  768 (NW = 8) or 512 (NW = 4) threads.
+// FZ = 1 / 2 (one sub-tile per consumer wave): the GroupNorm-finishing epilogues of conv3x3_split_kernel, run by the consumer waves;
+// the producers' code, their waits and the one barrier per stage are the same.
 // ---------------------------------------------------------------------------------------------------
-template <int NW, int MODE, int NPW, int MS>
+template <int NW, int MODE, int NPW, int MS, int FZ = 0>
 __global__ void __launch_bounds__(64 * (NW / MS) + 64 * NPW) conv3x3_split_ws_kernel(ConvGeom g, const float* __restrict__ src0, const float* __restrict__ src1,
                                                                         const unsigned short* __restrict__ ws, const float* __restrict__ bias,
                                                                         const float* __restrict__ residual, float* __restrict__ out,
@@ -447,6 +481,7 @@ __global__ void __launch_bounds__(64 * (NW / MS) + 64 * NPW) conv3x3_split_ws_ke
   constexpr int KA = 2 * NW / NPW;                          // staging units (8 channels of one pixel) per producer thread
   constexpr int NWC = NW / MS;                              // consumer waves (NW = 32-pixel sub-tiles of the workgroup's tile, MS per wave)
   static_assert(MS == 1 || MS == 2, "sub-tiles per consumer wave");
+  static_assert(FZ == 0 || (MODE == 0 && MS == 1), "the GroupNorm-finishing epilogues (FZ = 1 forward, 2 backward): 3x3 / stride 1, one sub-tile per wave");
   static_assert(NPW == 4 || NPW == 8, "producer waves: one or two per SIMD");
   static_assert(KA >= 1 && NB >= 1, "every producer wave stages something");
   constexpr int SLAB = T * 32 * kSplitRow, BPAD = (MODE == 0) ? 512 : 2048;
@@ -629,7 +664,9 @@ __global__ void __launch_bounds__(64 * (NW / MS) + 64 * NPW) conv3x3_split_ws_ke
   for (int ms = 0; ms < MS; ++ms)
     for (int r = 0; r < 16; ++r) { acc[ms][r] = 0.f; accb[ms][r] = 0.f; }
   const int tr_c = (trace && blockIdx.x == 0 && lane == 0 && wave == 0) ? 0 : -1;
+  double* const fz_rows = reinterpret_cast<double*>(smem + 2 * (size_t)bufsz);   // behind the two buffers (launched with ConvGeom::gf_out / bf_dx only)
   for (int s = 0; s < nst; ++s) {
+    bool stage_synced = false;
     if (tr_c >= 0 && s < 32) g_stream_trace[tr_c + 4 * s + 0] = clock64();
     const float bv_pre = (bias ? bias : reinterpret_cast<const float*>(ws))[cs.tn * 32 + l31];
     int oy0 = 0, ox0 = 0;
@@ -689,6 +726,13 @@ __global__ void __launch_bounds__(64 * (NW / MS) + 64 * NPW) conv3x3_split_ws_ke
       const int b0 = cs.bi * g.NI, vy0 = cs.rt * g.TH, n0 = cs.tn * 32;
       const int c = n0 + l31;
       const float bv = bias ? bv_pre : 0.f;
+      // GroupNorm finished in the workgroup (ConvGeom::gf_out / bf_dx, k_conv_epilogue.h; one sub-tile per consumer wave only): the
+      // tile's values stay in fz_v / fzk, the wave's sub-tile is `wave`
+      constexpr bool fz_fwd = FZ == 1, fz_bwd = FZ == 2;
+      bool fz_live = false;
+      int fz_b = 0, fz_pin = 0;
+      float fz_v[16];
+      FzBwdKeep fzk;
 #pragma unroll
       for (int ms = 0; ms < MS; ++ms) {
 #pragma unroll
@@ -706,11 +750,19 @@ __global__ void __launch_bounds__(64 * (NW / MS) + 64 * NPW) conv3x3_split_ws_ke
           gs1 += v[r];
           gs2 += v[r] * v[r];
         }
-        if (g.gn_part) PIDM_GN_PARTIAL(gs1, gs2, b, pin, c)
-        if (g.bn_part) {
+        if (FZ == 0 && g.gn_part) PIDM_GN_PARTIAL(gs1, gs2, b, pin, c)
+        if (fz_fwd) {
+          pidm_fz_fwd_put(g, fz_rows, wave, gs1, gs2, half, l31);
+#pragma unroll
+          for (int r = 0; r < 16; ++r) fz_v[r] = v[r];
+        }
+        if (FZ == 0 && g.bn_part) {
           const float* xrow = g.bn_x + ((size_t)b * g.Ho * g.Wo + pin) * g.Cout + c;
           PIDM_BN_PARTIAL(acc[ms], bv, b, pin, c, xrow, g.Cout, (g.bn_res && residual != nullptr), residual + ((size_t)b * g.Ho * g.Wo + pin) * g.ldr + c, g.ldr)
         }
+        if (fz_bwd) pidm_fz_bwd_put(g, fz_rows, wave, acc[ms], bv, b, c, g.bn_x + ((size_t)b * g.Ho * g.Wo + pin) * g.Cout + c, half, l31, fzk);
+        fz_live = true; fz_b = b; fz_pin = pin;
+        if (!fz_bwd) {                     // (the fused backward writes the GroupNorm's input gradient instead of this tensor)
         const bool odd1 = (l31 & 1) != 0, odd2 = (l31 & 2) != 0;
         const size_t opix = (size_t)b * g.sob + (size_t)pin * g.sox + n0 + 4 * (l31 >> 2);
         const size_t rpix = ((size_t)b * g.Ho * g.Wo + pin) * g.ldr + n0 + 4 * (l31 >> 2);
@@ -735,13 +787,30 @@ __global__ void __launch_bounds__(64 * (NW / MS) + 64 * NPW) conv3x3_split_ws_ke
             *reinterpret_cast<f32x4*>(out + opix + (size_t)prow * g.sox) = o;
           }
         }
+        }
       }
       for (int r = 0; r < 16; ++r) { acc[ms][r] = 0.f; accb[ms][r] = 0.f; }
       }
+      if (fz_fwd || fz_bwd) {
+        // this stage's barrier, taken here (every consumer wave takes this branch together - it depends on kernel arguments and the
+        // stage only - and the producers meet them at their own barrier of the stage): what crosses it lives in this block and not
+        // around the stage loop; behind it the sums of all waves are in LDS.  The rows are written again NCH >= 2 stages on, behind
+        // the next barrier at the earliest.
+        if (tr_c >= 0 && s < 32) g_stream_trace[tr_c + 4 * s + 2] = clock64();
+        split_cursor_next<MODE>(cs, NCH, CCH, g.tiles_m, tpi, ntn);
+        __syncthreads();             // buffer (s+1)&1 complete, buffer s&1 free
+        stage_synced = true;
+        if (fz_live) {
+          if (fz_fwd) pidm_fz_fwd_finish(g, fz_rows, wave, fz_b, fz_pin, n0, fz_v, half, l31);
+          else pidm_fz_bwd_finish(g, fz_rows, wave, fz_b, fz_pin, n0, fzk, half, l31);
+        }
+      }
     }
+    if (!stage_synced) {
     if (tr_c >= 0 && s < 32) g_stream_trace[tr_c + 4 * s + 2] = clock64();
     split_cursor_next<MODE>(cs, NCH, CCH, g.tiles_m, tpi, ntn);
     __syncthreads();               // buffer (s+1)&1 complete, buffer s&1 free
+    }
     if (tr_c >= 0 && s < 32) g_stream_trace[tr_c + 4 * s + 3] = clock64();
     char* tswap = bufc; bufc = bufn; bufn = tswap;
   }
@@ -1146,10 +1215,27 @@ static int split_npw(bool one_consumer_per_simd) {
   if (!e) return one_consumer_per_simd ? 8 : 4;
   return atoi(e) == 4 ? 4 : 8;
 }
-template <int NW, int MODE>
+// FZ = 1 / 2: the instantiations whose epilogue finishes a GroupNorm (forward / backward; ConvGeom::gf_out / bf_dx) - kernels of their
+// own, so that every other launch runs the code it always ran; one sub-tile per consumer wave
+template <int NW, int MODE, int FZ = 0>
 static void launch_split_ws(int wgs, size_t lds, hipStream_t st, const ConvGeom& gs, const float* src0, const float* src1,
                             const unsigned short* wsplit, const float* bias, const float* residual, float* out, int n_items, int ipw,
                             int trace) {
+  if constexpr (FZ != 0) {
+    static bool attr_fz = false;
+    if (!attr_fz) {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_split_ws_kernel<NW, MODE, 4, 1, FZ>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_split_ws_kernel<NW, MODE, 8, 1, FZ>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
+      attr_fz = true;
+    }
+    if (split_npw(NW == 4) == 8)
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_split_ws_kernel<NW, MODE, 8, 1, FZ>), dim3(wgs), dim3(64 * NW + 64 * 8), lds, st, gs, src0, src1, wsplit,
+                         bias, residual, out, n_items, ipw, trace);
+    else
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_split_ws_kernel<NW, MODE, 4, 1, FZ>), dim3(wgs), dim3(64 * NW + 64 * 4), lds, st, gs, src0, src1, wsplit,
+                         bias, residual, out, n_items, ipw, trace);
+    return;
+  }
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_split_ws_kernel<NW, MODE, 4, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
@@ -1819,8 +1905,34 @@ int launch_conv(const ConvGeom& g, const float* src0, const float* src1, const f
         const int npixA = gs.NI * gs.IHt * gs.IWt, SEG = gs.NI * gs.IHt * gs.Wv;
         gs.rpad = split_row_pad(gs.Wv);
         gs.xcd = split_xcd_order();
-        const size_t lds = (size_t)2 * ((npixA + 9 * 32) * kSplitRow + gs.NI * gs.IHt * gs.rpad + 512);
+        size_t lds = (size_t)2 * ((npixA + 9 * 32) * kSplitRow + gs.NI * gs.IHt * gs.rpad + 512);
         if (!(SEG % 32 == 0 && 2 * SEG >= 64 * nw && 2 * SEG <= 128 * nw && lds <= 160 * 1024 - 256)) continue;
+        // GroupNorm finished inside the workgroup (ConvGeom::gf_out / bf_dx, a request): the tile is whole images (TH = the image
+        // height; an image = cpi of the tile's nw 32-pixel sub-tiles), a group lies inside the tile's 32 channels, the rows of sums
+        // fit behind the buffers, one sub-tile per wave, and at least two stages per item (the rows are reused an item later).
+        // Otherwise - or with PIDM_NO_GN_FUSED=1 - the launch leaves the partial sums (gn_part / bn_part) as without the request.
+        int fzk = 0;                       // the kernel variant: 0 plain, 1 / 2 finishes the forward / backward GroupNorm
+        {
+          const bool fwd = gs.gf_out != nullptr;
+          bool fz = false;
+          if (fwd || gs.bf_dx) {
+            const int HW = gs.Ho * gs.Wo, cpi = HW / 32, cpg = fwd ? gs.gn_cpg : gs.bn_cpg;
+            const char* nf = knob("PIDM_NO_GN_FUSED");
+            fz = !(nf && atoi(nf)) && gs.TH == gs.Hv && gs.Hv == gs.Ho && gs.Wv == gs.Wo && HW % 32 == 0 && is_pow2(cpi) && cpi <= nw &&
+                 cpi == (fwd ? gs.gn_nchunk : gs.bn_nchunk) && is_pow2(cpg) && cpg <= 32 && gs.Cin >= 32 && !residual && !gs.bn_res &&
+                 !(fwd && gs.bf_dx) && !(split_ws_on(nw) && nw == 8 && split_ms() == 2) && gs.sox == gs.Cout &&
+                 gs.sob == (long)HW * gs.Cout && lds + fz_lds_bytes(nw) <= 160 * 1024 - 256;
+          }
+          if (fz) {
+            lds += fz_lds_bytes(nw);
+            if (fwd) gs.gn_part = nullptr; else gs.bn_part = nullptr;
+            if (g.fused_out) *g.fused_out = 1;
+            fzk = fwd ? 1 : 2;
+          } else {
+            gs.gf_out = nullptr;
+            gs.bf_dx = nullptr;
+          }
+        }
         const int n_items = gs.tiles_m * (g.Cout / 32);
         const bool prof = prof_enabled();
         static bool attr_p = false;
@@ -1835,7 +1947,35 @@ int launch_conv(const ConvGeom& g, const float* src0, const float* src1, const f
         const int trace = knob("PIDM_STREAM_TRACE") ? 1 : 0;
         if (knob("PIDM_TRACE_CONV")) fprintf(stderr, "[pidm]   -> conv3x3_split_kernel<%d>, %d items over %d workgroups, %zu B LDS\n", nw, n_items, wgs, lds);
         if (prof) prof_begin_launch(2, 2.0 * g.B * g.Hv * g.Wv * (double)g.Cout * g.Kw * 9, st);
-        if (split_ws_on(nw)) {
+        if (fzk) {
+          // (kernels of their own: their dynamic-LDS limit is raised on first use)
+          static bool attr_fz = false;
+          if (!attr_fz) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_split_kernel<8, 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_split_kernel<4, 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_split_kernel<8, 0, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_split_kernel<4, 0, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
+            attr_fz = true;
+          }
+          const float* s1 = src1 ? src1 : src0;
+          if (split_ws_on(nw)) {
+            PIDM_PROF_NAME(nw == 8 ? "conv3x3_split_ws_kernel<8, 0> +gn" : "conv3x3_split_ws_kernel<4, 0> +gn");
+            if (nw == 8 && fzk == 1) launch_split_ws<8, 0, 1>(wgs, lds, st, gs, src0, s1, wsplit, bias, residual, out, n_items, ipw, trace);
+            else if (nw == 8) launch_split_ws<8, 0, 2>(wgs, lds, st, gs, src0, s1, wsplit, bias, residual, out, n_items, ipw, trace);
+            else if (fzk == 1) launch_split_ws<4, 0, 1>(wgs, lds, st, gs, src0, s1, wsplit, bias, residual, out, n_items, ipw, trace);
+            else launch_split_ws<4, 0, 2>(wgs, lds, st, gs, src0, s1, wsplit, bias, residual, out, n_items, ipw, trace);
+          } else {
+            PIDM_PROF_NAME(nw == 8 ? "conv3x3_split_kernel<8, 0> +gn" : "conv3x3_split_kernel<4, 0> +gn");
+#define PIDM_FZ_LAUNCH(NW_, FZ_)                                                                                                    \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_split_kernel<NW_, 0, FZ_>), dim3(wgs), dim3(64 * NW_), lds, st, gs, src0, s1, wsplit, bias, residual, \
+                     out, n_items, ipw, trace)
+            if (nw == 8 && fzk == 1) PIDM_FZ_LAUNCH(8, 1);
+            else if (nw == 8) PIDM_FZ_LAUNCH(8, 2);
+            else if (fzk == 1) PIDM_FZ_LAUNCH(4, 1);
+            else PIDM_FZ_LAUNCH(4, 2);
+#undef PIDM_FZ_LAUNCH
+          }
+        } else if (split_ws_on(nw)) {
           PIDM_PROF_NAME(nw == 8 ? "conv3x3_split_ws_kernel<8, 0>" : "conv3x3_split_ws_kernel<4, 0>");
           if (nw == 8) launch_split_ws<8, 0>(wgs, lds, st, gs, src0, src1 ? src1 : src0, wsplit, bias, residual, out, n_items, ipw, trace);
           else launch_split_ws<4, 0>(wgs, lds, st, gs, src0, src1 ? src1 : src0, wsplit, bias, residual, out, n_items, ipw, trace);
@@ -1984,6 +2124,62 @@ extern "C" int pidm_conv_forward_gn_partials(const pidm_conv_desc* d, const floa
   const int rc = launch_conv(g, src0, src1, w_packed, bias, nullptr, out, 0, as_stream(stream));
   if (rc < 0) return rc;
   return (ok && rc == 0) ? chunks : 0;
+}
+
+// One half of a ResnetBlock as the engine runs it (resblock_fwd / resblock_bwd, unet_engine.hip), for the parity tests.
+// Forward: a = conv(src) + bias, y = SiLU(FiLM(GroupNorm(a))) [+ res], stats = (mean, rstd) - the GroupNorm finished by the
+// convolution's workgroups where the launch is eligible (ConvGeom::gf_out; returns 1), else by launch_gn_stats / launch_gn_apply (0).
+extern "C" int pidm_conv_gn_forward(const pidm_conv_desc* d, const float* src0, const float* src1, const float* w_packed, const float* bias,
+                                    int groups, const float* gamma, const float* beta, const float* ss, const float* ssb, int ldss,
+                                    const float* res, float* a, float* y, float* stats, void* ws, void* stream) {
+  ConvGeom g;
+  if (geom_fwd(d, &g)) return -1;
+  const int HW = g.Ho * g.Wo, cpg = (groups > 0 && g.Cout % groups == 0) ? g.Cout / groups : 0;
+  int chunks = HW / 32, fused = 0;
+  const bool ok = g.Cout % 32 == 0 && cpg >= 4 && cpg <= 32 && (cpg & (cpg - 1)) == 0 && HW % 32 == 0 && g.nz == 1 && g.nph == 1 && g.os == 1 &&
+                  g.soc == 1 && g.KH == 3 && (32 % g.Wv == 0 || g.Wv % 32 == 0) && groups <= 64 && 256 % groups == 0;
+  if (ok) {
+    g.gn_part = reinterpret_cast<double*>(ws); g.gn_cpg = cpg; g.gn_G = groups; g.gn_nchunk = HW / 32; g.part_chunks_out = &chunks;
+    g.gf_out = y; g.gf_stats = stats; g.gf_gamma = gamma; g.gf_beta = beta; g.gf_ss = ss; g.gf_ssb = ssb; g.gf_ldss = ldss; g.gf_res = res;
+    g.gf_nl = 256 / groups;
+    g.fused_out = &fused;
+  }
+  const int rc = launch_conv(g, src0, src1, w_packed, bias, nullptr, a, 0, as_stream(stream));
+  if (rc < 0) return rc;
+  if (fused) return 1;
+  const int pc = (ok && rc == 0) ? chunks : 0;
+  if (!pc && launch_gn_stats(a, g.B, HW, g.Cout, groups, stats, ws, as_stream(stream))) return -1;
+  if (launch_gn_apply(a, stats, gamma, beta, ss, ssb, ldss, res, y, g.B, HW, g.Cout, groups, ws, as_stream(stream), pc)) return -1;
+  return 0;
+}
+// Backward: dy = the input gradient of the convolution described by d (a block's conv 2) from its output gradient g_c, dx = the
+// backward of y = SiLU(FiLM(GroupNorm(x))) at dy, dgb[B][2][C] / dss[B][ldss] its per-image dgamma | dbeta and FiLM rows - inside the
+// convolution where eligible (ConvGeom::bf_dx; returns 1, dy is not written), else launch_gn_bwd behind it (0).
+extern "C" int pidm_conv_dgrad_gn_backward(const pidm_conv_desc* d, const float* g_c, const float* w_packed_dgrad, const float* x,
+                                           const float* stats, int groups, const float* gamma, const float* beta, const float* ss,
+                                           const float* ssb, int ldss, float* dss, float* dgb, float* dy, float* dx, void* ws, void* stream) {
+  ConvGeom g;
+  int kind;
+  if (geom_dgrad(d, d->Cout, d->C0 + d->C1, &g, &kind)) return -1;
+  const int HW = g.Ho * g.Wo, C = g.Cout, cpg = (groups > 0 && C % groups == 0) ? C / groups : 0;
+  int chunks = HW / 32, fused = 0;
+  const bool ok = C % 32 == 0 && cpg >= 1 && HW % 32 == 0 && g.nz == 1 && g.nph == 1 && g.os == 1 && g.soc == 1 && g.KH == 3 && C <= 1024 &&
+                  (C & (C - 1)) == 0 && groups <= 64 && 256 % groups == 0;
+  if (ok) {
+    g.bn_part = reinterpret_cast<double*>(ws);
+    g.bn_x = x; g.bn_stats = stats; g.bn_gamma = gamma; g.bn_beta = beta; g.bn_ss = ss; g.bn_ssb = ssb; g.bn_ldss = ldss;
+    g.bn_cpg = cpg; g.bn_G = groups; g.bn_nchunk = HW / 32; g.part_chunks_out = &chunks;
+    g.bf_dx = dx; g.bf_dgb = dgb; g.bf_dss = dss; g.bf_nl = C < 256 ? 256 / C : 1;
+    g.fused_out = &fused;
+  }
+  const int rc = launch_conv(g, g_c, nullptr, w_packed_dgrad, nullptr, nullptr, dy, 0, as_stream(stream));
+  if (rc < 0) return rc;
+  if (fused) return 1;
+  ReduceQueue q;       // (the per-image rows stay in dgb: their sum over the batch is the caller's)
+  if (launch_gn_bwd(x, dy, stats, gamma, beta, ss, ssb, ldss, dss, dx, nullptr, nullptr, g.B, HW, C, groups, ws, as_stream(stream), dgb, &q,
+                    (ok && rc == 0) ? chunks : 0))
+    return -1;
+  return 0;
 }
 
 extern "C" int pidm_conv_dgrad(const pidm_conv_desc* d, const float* dy, int ld_dy, const float* w_packed_dgrad,

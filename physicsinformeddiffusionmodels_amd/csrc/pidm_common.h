@@ -266,6 +266,30 @@ struct ConvGeom {
   // (Ho*Wo/32 for the tile kernels - one per wave tile; one per strip for the row-streaming kernel, k_conv_rs.hip, which sums over the
   // rows of a strip first).  A caller that passes null gets Ho*Wo/32 chunks or no epilogue.
   int* part_chunks_out;
+  // The same two GroupNorms FINISHED inside the workgroup (split-form 3x3 kernels of k_conv.hip, stride-1 form; k_conv_epilogue.h):
+  // where a workgroup's pixel tile holds whole images and its 32 output channels whole groups, the sums above never leave the
+  // workgroup - they cross the stage barrier in LDS, and the waves that hold the tile in registers normalise it themselves.
+  // A REQUEST: the caller fills these next to gn_part / bn_part, launch_conv decides per launch (whole images per tile, groups
+  // inside 32 channels, room in LDS; PIDM_NO_GN_FUSED=1: never) and says so in *fused_out; a launch that is not fused runs the
+  // gn_part / bn_part path exactly as without the request.
+  // forward (gn_cpg / gn_G / gn_nchunk as above): gf_out = SiLU(FiLM(GroupNorm(out))) [+ gf_res], gf_stats[b][g] = (mean, rstd);
+  // `out` itself is still written (the backward normalises it again)
+  float* gf_out;
+  float* gf_stats;
+  const float* gf_gamma;
+  const float* gf_beta;
+  const float* gf_ss;     // FiLM activations [B][gf_ldss] (scale | shift) and their bias [2*Cout]; null: none
+  const float* gf_ssb;
+  const float* gf_res;    // added after the SiLU (laid out like gf_out); null: none
+  int gf_ldss;
+  int gf_nl;              // partial sums are added in the order of gn_finalize_stats (k_norm.hip): gf_nl interleaved runs, then the runs
+  // backward (bn_x .. bn_nchunk as above, no residual): bf_dx = the GroupNorm's input gradient (gn_bwd_apply_kernel's dx) INSTEAD of
+  // `out`, which is not written; bf_dgb[b][2][Cout] and bf_dss[b][bn_ldss] (null without FiLM) = that kernel's per-image rows
+  float* bf_dx;
+  float* bf_dgb;
+  float* bf_dss;
+  int bf_nl;              // (order of gn_bwd_apply_kernel's chunk sum)
+  int* fused_out;         // host side only: set to 1 by a launch that finished the GroupNorm itself
 };
 
 // Geometry of one weight-gradient launch (k_conv.hip, k_wgrad_rs.hip): dW[m][t][n] = sum_p dY[p][m] * X[p (+tap)][n]

@@ -684,26 +684,46 @@ static int conv_fwd(Run& r, const ConvLayer& L, const float* x0, const float* x1
 // gn_apply finalises them - one launch and one full read of the activation less than conv -> gn_stats -> gn_apply.
 // *part_chunks = chunks per image written (0: not produced - shape not eligible or kernel without the epilogue; the caller
 // then runs launch_gn_stats).
-static int conv_fwd_gn(Run& r, const ConvLayer& L, const float* x0, const float* x1, float* out, int G, int* part_chunks) {
+// fz: the GroupNorm itself as a request to the convolution (ConvGeom::gf_out: at the levels where a workgroup's tile holds whole
+// images the kernel normalises its tile before it lets go of it).  fz->done says whether the launch did: y and stats are then
+// written and the caller runs neither launch_gn_stats nor launch_gn_apply; otherwise everything is as without the request.
+struct GnFused {
+  const float *gamma, *beta, *ss, *ssb;   // ss / ssb: FiLM rows [B][ldss] and their bias (null: none)
+  int ldss;
+  const float* res;                        // added behind the SiLU (null: none)
+  float *y, *stats;
+  bool done;
+};
+static int conv_fwd_gn(Run& r, const ConvLayer& L, const float* x0, const float* x1, float* out, int G, int* part_chunks,
+                       GnFused* fz = nullptr) {
   const bool off = knob("PIDM_NO_GN_EPILOGUE") != nullptr;
   *part_chunks = 0;
+  if (fz) fz->done = false;
   ConvGeom g;
   if (geom_fwd_layer(L, r.B, 0, &g)) return -1;
   const int HW = g.Ho * g.Wo, cpg = (G > 0 && L.Cout % G == 0) ? L.Cout / G : 0;
   int chunks = HW / 32;               // (the row-streaming kernel writes one chunk per strip: ConvGeom::part_chunks_out)
   const bool ok = !off && L.Cout % 32 == 0 && cpg >= 4 && cpg <= 32 && (cpg & (cpg - 1)) == 0 && HW % 32 == 0 && g.nz == 1 &&
                   g.nph == 1 && g.os == 1 && g.soc == 1 && g.KH == 3 && (32 % g.Wv == 0 || g.Wv % 32 == 0);
+  int fused = 0;
   if (ok) {
     g.gn_part = reinterpret_cast<double*>(r.scratch);
     g.gn_cpg = cpg;
     g.gn_G = G;
     g.gn_nchunk = HW / 32;
     g.part_chunks_out = &chunks;
+    if (fz && G <= 64 && 256 % G == 0) {
+      g.gf_out = fz->y; g.gf_stats = fz->stats; g.gf_gamma = fz->gamma; g.gf_beta = fz->beta;
+      g.gf_ss = fz->ss; g.gf_ssb = fz->ssb; g.gf_ldss = fz->ldss; g.gf_res = fz->res;
+      g.gf_nl = 256 / G;              // (gn_finalize_stats: 256 / G threads share a group's chunk sum)
+      g.fused_out = &fused;
+    }
   }
   if (r.dry) return 0;
   const int rc = launch_conv(g, x0, x1, r.wpack + L.off_f, L.b >= 0 ? r.U->P[L.b] : nullptr, nullptr, out, 0, r.st);
   if (rc < 0) return rc;
-  if (ok && rc == 0) *part_chunks = chunks;
+  if (ok && rc == 0 && fused) fz->done = true;
+  else if (ok && rc == 0) *part_chunks = chunks;
   return 0;
 }
 
@@ -731,25 +751,34 @@ static int resblock_fwd(Run& r, ResBlock& m, const float* x0, const float* x1, f
   m.x0 = x0; m.x1 = x1;
   m.a = act_alloc(r, n);
   int pc1 = 0, pc2 = 0;
-  if (conv_fwd_gn(r, m.c1, x0, x1, m.a, G, &pc1)) return -1;
+  // (the buffers of both GroupNorms are taken in front of their convolutions, in the order they always had: at the small levels the
+  // convolution finishes the GroupNorm itself - GnFused - and needs its destination)
   m.st1 = act_alloc(r, (size_t)B * G * 2);
-  if (!pc1) RUN(launch_gn_stats(m.a, B, HW, Co, G, m.st1, r.scratch, r.st));
   // inference (no tape): GroupNorm + FiLM + SiLU in place - half the footprint of the pass in the caches, a smaller workspace
   // (PIDM_NO_GN_INPLACE=1: off)
   const bool inplace = !r.train && !knob_on("PIDM_NO_GN_INPLACE");
   m.bact = inplace ? m.a : act_alloc(r, n);
   const float* ss = m.has_mlp ? U->ss + m.ss_off : nullptr;
   const float* ssb = m.has_mlp ? U->P[m.mlpb] : nullptr;
-  RUN(launch_gn_apply(m.a, m.st1, U->P[m.gn1w], U->P[m.gn1b], ss, ssb, U->ss_total, nullptr, m.bact, B, HW, Co, G, r.scratch, r.st, pc1));
+  GnFused f1 = {U->P[m.gn1w], U->P[m.gn1b], ss, ssb, U->ss_total, nullptr, m.bact, m.st1, false};
+  if (conv_fwd_gn(r, m.c1, x0, x1, m.a, G, &pc1, &f1)) return -1;
+  if (!f1.done) {
+    if (!pc1) RUN(launch_gn_stats(m.a, B, HW, Co, G, m.st1, r.scratch, r.st));
+    RUN(launch_gn_apply(m.a, m.st1, U->P[m.gn1w], U->P[m.gn1b], ss, ssb, U->ss_total, nullptr, m.bact, B, HW, Co, G, r.scratch, r.st, pc1));
+  }
   m.c = (inplace && !m.has_res) ? out : act_alloc(r, n);      // (in place: the second convolution writes the block's output buffer)
-  if (conv_fwd_gn(r, m.c2, m.bact, nullptr, m.c, G, &pc2)) return -1;
   m.st2 = act_alloc(r, (size_t)B * G * 2);
-  if (!pc2) RUN(launch_gn_stats(m.c, B, HW, Co, G, m.st2, r.scratch, r.st));
+  float* d = m.has_res ? (inplace ? m.c : r.tmp.alloc(n)) : nullptr;
+  // GroupNorm 2 (+ x0, or the plain tensor the res_conv launch then adds to); in front of an attention block it stays a kernel of its
+  // own, whether that block's LayerNorm rides in it (ln_out) or not: the LayerNorm needs all channels of a pixel, which span
+  // workgroups, and PIDM_NO_GN_LN_FUSE=1 must change nothing but the LayerNorm's place
+  GnFused f2 = {U->P[m.gn2w], U->P[m.gn2b], nullptr, nullptr, 0, m.has_res ? nullptr : x0, m.has_res ? d : out, m.st2, false};
+  if (conv_fwd_gn(r, m.c2, m.bact, nullptr, m.c, G, &pc2, next_attn ? nullptr : &f2)) return -1;
+  if (!f2.done && !pc2) RUN(launch_gn_stats(m.c, B, HW, Co, G, m.st2, r.scratch, r.st));
   if (m.has_res) {
-    float* d = inplace ? m.c : r.tmp.alloc(n);
-    RUN(launch_gn_apply(m.c, m.st2, U->P[m.gn2w], U->P[m.gn2b], nullptr, nullptr, 0, nullptr, d, B, HW, Co, G, r.scratch, r.st, pc2));
+    if (!f2.done) RUN(launch_gn_apply(m.c, m.st2, U->P[m.gn2w], U->P[m.gn2b], nullptr, nullptr, 0, nullptr, d, B, HW, Co, G, r.scratch, r.st, pc2));
     if (conv_fwd(r, m.cr, x0, x1, d, out)) return -1;
-  } else {
+  } else if (!f2.done) {
     RUN(launch_gn_apply(m.c, m.st2, U->P[m.gn2w], U->P[m.gn2b], nullptr, nullptr, 0, x0, out, B, HW, Co, G, r.scratch, r.st, pc2,
                         ln_out ? U->P[next_attn->gamma] : nullptr, ln_out));
   }
@@ -778,7 +807,9 @@ static long lap_knob_signature() {
   return 8 * (off ? -1 : (long)min_n) + (g && !atoi(g) ? 1 : 0) + (gb ? (atoi(gb) ? 2 : 4) : 0) + 1000003L * (gw ? atoi(gw) : 0) +
          7919L * (wgrad_group_on(1, 1, false) ? 1 : 0) +  // (grouped weight gradients keep the backward arena's frames)
          104729L * (knob("PIDM_WGRAD_GROUP_MAXWORK") ? atol(knob("PIDM_WGRAD_GROUP_MAXWORK")) % 65521 : 0) +
-         15485863L * (knob("PIDM_LAP_NPER_DIV") ? atol(knob("PIDM_LAP_NPER_DIV")) % 8 : 0);   // (scratch of the pixel-sum kernels)
+         15485863L * (knob("PIDM_LAP_NPER_DIV") ? atol(knob("PIDM_LAP_NPER_DIV")) % 8 : 0) +   // (scratch of the pixel-sum kernels)
+         32452843L * (knob_on("PIDM_NO_GN_FUSED") ? 1 : 0);   // (GroupNorm finished inside the convolution: same buffers either way;
+                                                              //  listed so that a flip on a live handle starts from fresh plans)
 }
 static bool attn_shape_projectable(const AttnBlock& a, int heads) { return !a.mid && a.out.b >= 0 && lap_ok(a.H * a.H, heads, a.C, a.C); }
 // decided by the FORWARD (and stored in AttnBlock::projected); the backward replays the stored decision
@@ -1049,6 +1080,14 @@ static int resblock_bwd(Run& r, ResBlock& m, const float* g_out, float* g_x, flo
   // with (the first of its two passes over x and dy).  Needs the deferred-reduction arena: otherwise the weight-gradient
   // partials of conv2 live in r.scratch, where the sums go.
   int pcb = 0;
+  // g_c is dead on THIS stream after the two uses above, but the side-stream wgrad of c2 may still be reading it
+  float* g_a = r.keep_frames() ? r.tmp.alloc(n) : g_c;
+  // At the levels where a workgroup's tile holds whole images that launch finishes GroupNorm 1's backward itself (ConvGeom::bf_dx):
+  // it writes g_a and the per-image dgamma / dbeta / FiLM rows, g_b is never written and launch_gn_bwd is not called.  Where g_a IS
+  // g_c - which that convolution reads - the gradient goes to g_b's buffer instead; with kept frames (whenever weight gradients are
+  // queued for a grouped launch) it is g_a's own, so the queued descriptors hold the same pointers fused or not.
+  float* const g_a_fused = (g_a == g_c) ? g_b : g_a;
+  int fused = 0;
   {
     const bool off = knob("PIDM_NO_GN_EPILOGUE") != nullptr || knob("PIDM_NO_BN_EPILOGUE") != nullptr;
     pidm_conv_desc d = desc_of(m.c2, r.B);
@@ -1065,17 +1104,29 @@ static int resblock_bwd(Run& r, ResBlock& m, const float* g_out, float* g_x, flo
       g.bn_ss = ss; g.bn_ssb = ssb; g.bn_ldss = U->ss_total;
       g.bn_cpg = cpg; g.bn_G = G; g.bn_nchunk = HW / 32;
       g.part_chunks_out = &chunks;
+      if (r.q() && dgb1 && Co <= 1024 && (Co & (Co - 1)) == 0 && G <= 64 && 256 % G == 0) {   // (what launch_gn_bwd accepts)
+        g.bf_dx = g_a_fused;
+        g.bf_dgb = dgb1;
+        g.bf_dss = m.has_mlp ? dss + m.ss_off : nullptr;
+        g.bf_nl = Co < 256 ? 256 / Co : 1;      // (gn_bwd_apply_kernel: 256 / C threads share a channel's chunk sum)
+        g.fused_out = &fused;
+      }
     }
     if (!r.dry) {
       const int rc = launch_conv(g, g_c, nullptr, r.wpack + m.c2.off_d, nullptr, nullptr, g_b, 0, r.st);
       if (rc < 0) return rc;
-      if (ok && rc == 0) pcb = chunks;
+      if (ok && rc == 0 && !fused) pcb = chunks;
     }
   }
-  // g_c is dead on THIS stream after the two uses above, but the side-stream wgrad of c2 may still be reading it
-  float* g_a = r.keep_frames() ? r.tmp.alloc(n) : g_c;
-  RUN(launch_gn_bwd(m.a, g_b, m.st1, U->P[m.gn1w], U->P[m.gn1b], ss, ssb, U->ss_total, m.has_mlp ? dss + m.ss_off : nullptr,
-                    g_a, U->G[m.gn1w], U->G[m.gn1b], B, HW, Co, G, r.scratch, r.st, dgb1, r.q(), pcb));
+  if (fused) {
+    g_a = g_a_fused;
+    // the reductions launch_gn_bwd queues: dgamma[c] = sum_b dgb[b][0][c], dbeta[c] = sum_b dgb[b][1][c]
+    r.q()->push(dgb1, U->G[m.gn1w], nullptr, nullptr, (size_t)2 * Co, B, 1, Co, 1, 1, Co);
+    r.q()->push(dgb1 + Co, U->G[m.gn1b], nullptr, nullptr, (size_t)2 * Co, B, 1, Co, 1, 1, Co);
+  } else {
+    RUN(launch_gn_bwd(m.a, g_b, m.st1, U->P[m.gn1w], U->P[m.gn1b], ss, ssb, U->ss_total, m.has_mlp ? dss + m.ss_off : nullptr,
+                      g_a, U->G[m.gn1w], U->G[m.gn1b], B, HW, Co, G, r.scratch, r.st, dgb1, r.q(), pcb));
+  }
   if (conv_wgrad(r, m.c1, m.x0, m.x1, g_a)) return -1;
   const float* res1 = g_out;
   if (m.has_res) {
@@ -1542,6 +1593,9 @@ static int plan_sizes(pidm_unet* U, int B, int training, size_t* tape_bytes, siz
     U->knob_sig = sig;
     U->wq_table_dev = nullptr;   // (the layout the grouped tables were uploaded under is gone with the plans)
     for (auto& t : U->wq_table) t.clear();
+    // ... and a backward graph captured under these knobs EARLIER reads both device tables as they were then, while the passes under
+    // the other knobs have uploaded theirs since: the next backward runs launch by launch (it uploads), replay resumes behind it
+    U->red_table_dev = nullptr;
   }
   auto& cache = U->ws_cache[training ? 1 : 0];
   auto it = cache.find(B);
