@@ -231,28 +231,22 @@ int pidm_mech_solve(const float* rho, const float* bcs, const float* kloc, int k
 int pidm_floating_material(const float* rho, float threshold, int nel, int32_t* n_components, int B, void* stream);
 
 /* Darcy training-data generation      replaces src/darcy_data_generation.py:118-163 (generate_sample: findiff assembly + dense lstsq)
- *   pidm_darcy_gen: per sample b, K = exp(basis^T z_b) (basis [q, P*P] row-major, sqrt(eigenvalue)-scaled KLE modes; z [B, q]) or,
- *                   when z is NULL, K = K_in[b] ([B, P*P]); then p = the least-squares solution of the reference's
- *                   (P^2+4P+1) x P^2 system: A p = -K p_00 - K_0 p_0 - K p_11 - K_1 p_1 = f_s (acc-2 stencils with spacings d0 /
- *                   d1; d1 < 0 for reverse_dy), boundary rows -D0 p (x-min), +D0 p (x-max), bc_sign D1 p (y-min), -bc_sign D1 p
- *                   (y-max) = 0, integral row int_w . p = 0.  Matrix-free column-scaled CGLS in fp64 on the system without the
- *                   integral row, then the constant-mode shift; stops at ||S A^T r|| <= rtol ||S A^T b|| or max_iter.
- *                   K_out [B, P*P] (may be NULL when z is NULL), p_out [B, P*P], res_mean [B] = mean |row residual| over all
- *                   P^2+4P+1 rows, iters [B], relres [B] = ||S A^T r|| / ||S A^T b|| (each of the last three may be NULL).
- *                   All arrays fp64.  8 <= P <= 64 (four fp64 fields of P^2 live in LDS), 1 <= q <= P^2.  No workspace: every
- *                   vector of the iteration stays on chip.
- *   pidm_darcy_gen_lds_bytes: dynamic LDS per workgroup (informational). */
-size_t pidm_darcy_gen_lds_bytes(int P);
-int pidm_darcy_gen(const double* basis, const double* z, int q, const double* K_in, int P, double d0, double d1, double bc_sign,
-                   const double* int_w, const double* f_s, int max_iter, double rtol, double* K_out, double* p_out,
-                   double* res_mean, int32_t* iters, double* relres, int B, void* stream);
-/*   pidm_darcy_gen_acc: the same system and the same method with findiff's classed operators of order acc in {2, 4, 6}
- *                   (src/darcy_data_generation.py:129-142, every FinDiff(..., acc=acc)): rows i < acc/2 forward, rows
- *                   i > P-1-acc/2 backward, the others central; central and one-sided first-derivative stencils have acc+1 taps,
- *                   one-sided second-derivative stencils acc+2.  K_0 and K_1 come from the same operators.  Arguments as
- *                   pidm_darcy_gen, plus (this entry and pidm_darcy_gen_periodic run one solver, csrc/k_darcy_gen_cgls.h, with
- *                   the 1-D operators of csrc/k_darcy_gen_acc.hip / csrc/k_darcy_gen_per.hip):
- *                   launch protocol - one call runs at most iters_this_launch (>= 1) CGLS iterations per sample that is not done
+ *   pidm_darcy_gen_acc: per sample b, K = exp(basis^T z_b) (basis [q, P*P] row-major, sqrt(eigenvalue)-scaled KLE modes; z [B, q],
+ *                   1 <= q <= P^2) or, when z is NULL, K = K_in[b] ([B, P*P]); then p = the least-squares solution of the
+ *                   reference's (P^2+4P+1) x P^2 system: A p = -K p_00 - K_0 p_0 - K p_11 - K_1 p_1 = f_s (spacings d0 / d1;
+ *                   d1 < 0 for reverse_dy), boundary rows -D0 p (x-min), +D0 p (x-max), bc_sign D1 p (y-min), -bc_sign D1 p
+ *                   (y-max) = 0, integral row int_w . p = 0 (f_s, int_w [P*P]).  The 1-D operators are findiff's classed ones of
+ *                   order acc in {2, 4, 6} (src/darcy_data_generation.py:129-142, every FinDiff(..., acc=acc)): rows i < acc/2
+ *                   forward, rows i > P-1-acc/2 backward, the others central; central and one-sided first-derivative stencils
+ *                   have acc+1 taps, one-sided second-derivative stencils acc+2.  K_0 and K_1 come from the same operators.
+ *                   Matrix-free column-scaled CGLS in fp64 on the system without the integral row, then the constant-mode shift;
+ *                   stops at ||S A^T r|| <= rtol ||S A^T b|| or max_iter.  Every vector of the iteration stays on chip (four
+ *                   fp64 fields of P^2 live in LDS).  This entry and pidm_darcy_gen_periodic run one solver,
+ *                   csrc/k_darcy_gen_cgls.h, with the 1-D operators of csrc/k_darcy_gen_acc.hip / csrc/k_darcy_gen_per.hip.
+ *                   Outputs: K_out [B, P*P] (may be NULL), p_out [B, P*P], res_mean [B] = mean |row residual| over all
+ *                   P^2+4P+1 rows, iters [B], relres [B] = ||S A^T r|| / ||S A^T b|| (each of the last three may be NULL).  All
+ *                   arrays fp64 on the device (iters int32); basis may be NULL when z is, K_in when z is given.
+ *                   Launch protocol - one call runs at most iters_this_launch (>= 1) CGLS iterations per sample that is not done
  *                   and returns; the caller repeats the call (first_launch = 0, every other argument unchanged) until done[b] != 0
  *                   for every b.  first_launch != 0 initialises `state` (whatever it held).  A sample is finished when it
  *                   converges (||S A^T r|| <= rtol ||S A^T b||) or reaches max_iter iterations in total; the launch that

@@ -85,9 +85,6 @@ class PidmLib:
         self._sig("pidm_mech_solve_ws_bytes", [i, i], sz)
         self._sig("pidm_mech_solve", [vp, vp, vp, i, vp, vp, i, f, f, f, i, C.c_double, vp, vp, vp, vp, vp, vp, i, vp])
         self._sig("pidm_floating_material", [vp, f, i, vp, i, vp])
-        self._sig("pidm_darcy_gen_lds_bytes", [i], sz)
-        self._sig("pidm_darcy_gen", [vp, vp, i, vp, i, C.c_double, C.c_double, C.c_double, vp, vp, i, C.c_double, vp, vp, vp, vp, vp,
-                                     i, vp])
         self._sig("pidm_darcy_gen_acc_state_bytes", [i, i], sz)
         self._sig("pidm_darcy_gen_acc_lds_bytes", [i, i], sz)
         self._sig("pidm_darcy_gen_acc", [vp, vp, i, vp, i, i, C.c_double, C.c_double, C.c_double, vp, vp, i, C.c_double, i, i, vp,

@@ -1,5 +1,5 @@
-// Darcy training-data generation at finite-difference order acc = 2, 4, 6: the solve of k_darcy_gen.hip with findiff's classed
-// operators of any of the three orders, in bounded, resumable launches.
+// Darcy training-data generation at finite-difference order acc = 2, 4, 6: the solve of k_darcy_gen_cgls.h with findiff's classed
+// operators of any of the three orders.
 //
 // Replaces (reference path): src/darcy_data_generation.py:129-163 with `acc` as the reference passes it to every
 // FinDiff(..., acc=acc).  The solve itself - system, row order, column scaling, deflation, stopping rule, launch protocol - is

@@ -1,9 +1,31 @@
-// The resumable fp64 CGLS solve shared by the Darcy generators of k_darcy_gen_acc.hip (findiff's classed operators) and
-// k_darcy_gen_per.hip (wrapped central operators): everything but the enumeration of a 1-D operator and of its transpose.
+// Darcy training-data generation for gfx950: KLE permeability synthesis and the fp64 least-squares pressure solve, shared by the
+// generators of k_darcy_gen_acc.hip (findiff's classed operators) and k_darcy_gen_per.hip (wrapped central operators): everything
+// but the enumeration of a 1-D operator and of its transpose.
 //
-// The system, the row order, the column scaling, the deflation by the integral row and the stopping rule are those of
-// k_darcy_gen.hip (read its header first).  A kernel file supplies `Ops`, a stateless struct per finite-difference order whose
-// static __device__ __forceinline__ members all take the coefficient table (in LDS) and P:
+// Replaces (reference path): src/darcy_data_generation.py:118-163 (generate_sample), which per sample assembles the dense
+// (P^2+4P+1) x P^2 system  [A; boundary rows; integral row] p = [f_s; 0; 0]  with findiff and solves it with
+// scipy.linalg.lstsq (7.2 s per 64x64 sample on a CPU core).  Here one workgroup per sample runs matrix-free CGLS in fp64:
+//
+//   A p        = -K p_00 - K_0 p_0 - K p_11 - K_1 p_1        (P^2 rows; D0, D00, D1, D11 and K_0 = D0 K, K_1 = D1 K from `Ops`)
+//   boundary   = -D0 p on the x-min row, +D0 p on x-max, bc_sign * D1 p on y-min, -bc_sign * D1 p on y-max   (4P rows)
+//   integral   = int_w . p                                                                                    (1 row)
+//
+// A_bc (the first P^2 + 4P rows) annihilates the constant field, so its least-squares solutions are q + c 1.  The solve
+// therefore runs on A_bc alone (the constant mode no longer sets the smallest singular value) and deflates at the end:
+// p = q - (int_w . q / int_w . 1) 1 is the least-squares solution of the full system (the integral row is then exactly
+// satisfied and leaves the other rows unchanged).  Columns are scaled by 1 / ||A_bc e_j||; CGLS on A_bc S y = b, p = S y,
+// stops at ||S A_bc^T r|| <= rtol ||S A_bc^T b|| or max_iter.  DESIGN.md section "Darcy data generation" has the measured
+// iteration counts.
+//
+// Everything stays on chip inside the loop: each lane keeps the search direction, scaled gradient, column scales, row
+// residuals and K, K_0, K_1 of its points in registers, its part of the iterate in LDS.  Neighbour access goes through one LDS
+// region of three fp64 fields: S p_hat while A is applied (F1 then holds A S p_hat until the step length is known), then
+// K r | K_0 r | K_1 r (the adjoint needs the neighbours' coefficients: A^T r = -D00^T (K r) - D0^T (K_0 r) - D11^T (K r) -
+// D1^T (K_1 r)) plus the 4P boundary residuals.  The table of unit-spacing stencil coefficients lives in LDS as well.  Two block
+// reductions per iteration (||A S p_hat||^2 and ||s||^2); their barriers also order the reuse of the LDS region.
+//
+// A kernel file supplies `Ops`, a stateless struct per finite-difference order whose static __device__ __forceinline__ members
+// all take the coefficient table (in LDS) and P:
 //
 //   TAB_DOUBLES, fill(TAB)                       size of the table of unit-spacing coefficients and its fill (one lane)
 //   taps(TAB, P, F, i, j, v0, v00, v1, v11)      forward tap sums of point (i, j) on the field F: D0 F, D00 F, D1 F, D11 F

@@ -3,13 +3,13 @@
 The reference draws a log-permeability field from a Karhunen-Loeve expansion (KLE) of an exponential covariance, assembles the
 dense (P^2+4P+1) x P^2 finite-difference system of -div(K grad p) = f_s with Neumann rows and an integral row, and solves it
 with `scipy.linalg.lstsq` (7.2 s per 64 x 64 sample on one CPU core).  Here the same functions keep their names and signatures,
-and the solve runs in `csrc/k_darcy_gen.hip`: one workgroup per sample, KLE synthesis and matrix-free column-scaled CGLS in
-fp64 ("Darcy data generation").  `acc` (the reference's finite-difference order, 2 / 4 / 6) selects the operators: 2 is
-that kernel; 4 and 6 run in `csrc/k_darcy_gen_acc.hip`, in launches of a bounded number of iterations that carry the CGLS state
-between them.  `bcs='periodic'` solves the system of `ResidualsDarcy(bcs='periodic')` instead - every operator central, on wrapped
-indices - in `csrc/k_darcy_gen_per.hip` (same launches), on permeability fields of a wrapped-distance covariance.  Host-side
-pieces are the grid, the eigendecomposition of the covariance (the reference's exact full `eigh`, cached) and the CSV writing.
-There is no CPU fallback for the solve.
+and the solve runs in `csrc/k_darcy_gen_cgls.h`: one workgroup per sample, KLE synthesis and matrix-free column-scaled CGLS in
+fp64 ("Darcy data generation"), in launches of a bounded number of iterations that carry the CGLS state between them.
+`acc` (the reference's finite-difference order, 2 / 4 / 6) selects the operators of `csrc/k_darcy_gen_acc.hip`.
+`bcs='periodic'` solves the system of `ResidualsDarcy(bcs='periodic')` instead - every operator central, on wrapped indices -
+with those of `csrc/k_darcy_gen_per.hip`, on permeability fields of a wrapped-distance covariance.  Host-side pieces are the
+grid, the eigendecomposition of the covariance (the reference's exact full `eigh`, cached) and the CSV writing.  There is no CPU
+fallback for the solve.
 
     python -m physicsinformeddiffusionmodels_amd.darcy_data_generation --n-samples 10000 --out ./data/darcy/train
     python -m physicsinformeddiffusionmodels_amd.darcy_data_generation --n-samples 10000 --out ./data/darcy/train4 --acc 4
@@ -35,9 +35,8 @@ ACCS = (2, 4, 6)
 BCS = ('none', 'periodic')     # the reference's main.py: bcs = 'none' # 'none', 'periodic'
 # max_iter=None: about twice the largest count measured at P = 64 (profiles/darcy_gen_bench_acc.txt)
 MAX_ITER_ACC = {2: MAX_ITER, 4: 1000000, 6: 4000000}     # measured maxima at P = 64, batch 256: 494 k (acc 4), 2.04 M (acc 6)
-# iterations per launch of the resumable entry for a batch of at most one workgroup per compute unit: a launch at P = 64, acc 6,
-# batch 256 then takes 0.60 s (30 us per iteration; bound: 2 s); _launch_acc divides it by
-# ceil(B / compute units)
+# iterations per launch for a batch of at most one workgroup per compute unit: a launch at P = 64, acc 6, batch 256 then takes
+# 0.60 s (30 us per iteration; bound: 2 s); _launch divides it by ceil(B / compute units)
 ITERS_PER_LAUNCH = 20000
 
 
@@ -124,8 +123,7 @@ def z_of_seed(seed, q):
 
 def min_pixels(acc, bcs='none'):
     """Smallest grid of order acc: rows below acc/2 use forward stencils, and the second-derivative one of row acc/2 - 1 reaches
-    column 3 acc/2 (9 at acc 6); 8 below that, as the second-order kernel.  Periodic: 8 at every order (the widest wrapped stencil
-    spans 7 points)."""
+    column 3 acc/2 (9 at acc 6); 8 below that.  Periodic: 8 at every order (the widest wrapped stencil spans 7 points)."""
     return 8 if bcs == 'periodic' else max(8, 3 * acc // 2 + 1)
 
 
@@ -221,28 +219,11 @@ def _outputs(B, P, device):
             torch.empty(B, dtype=torch.int32, device=device), torch.empty(B, **f64))
 
 
-def _launch(lib, device, prob, *, basis=None, z=None, K_in=None, B, max_iter, rtol, iters_per_launch=None, resumable=False,
-            stats=None):
-    if prob.acc != 2 or resumable or prob.periodic:
-        return _launch_acc(lib, device, prob, basis=basis, z=z, K_in=K_in, B=B, max_iter=max_iter, rtol=rtol,
-                           iters_per_launch=iters_per_launch, stats=stats)
-    P = prob.P
-    f_s, int_w = prob.on(device)
-    K, p, res, iters, relres = _outputs(B, P, device)
-    q = 0 if z is None else z.shape[1]
-    lib.check(lib.pidm_darcy_gen(ptr(basis), ptr(z), q, ptr(K_in), P, prob.d0, prob.d1, prob.bc_sign, ptr(int_w), ptr(f_s),
-                                 int(max_iter), float(rtol), ptr(K), ptr(p), ptr(res), ptr(iters), ptr(relres), B,
-                                 stream_ptr(device)), "pidm_darcy_gen")
-    if stats is not None:
-        stats.update(launches=1, longest_launch_s=None, iters_per_launch=None)
-    return K, p, res, iters, relres
-
-
-def _launch_acc(lib, device, prob, *, basis=None, z=None, K_in=None, B, max_iter, rtol, iters_per_launch=None, stats=None):
-    """The resumable entries (csrc/k_darcy_gen_acc.hip, or csrc/k_darcy_gen_per.hip for a periodic problem: same arguments, same
-    state): launches of at most `iters_per_launch` iterations per sample until every sample is done; the B done flags are read back
-    after each launch.  A batch larger than the device's compute units runs its workgroups one behind the other, so the budget of
-    a launch is divided by ceil(B / compute units)."""
+def _launch(lib, device, prob, *, basis=None, z=None, K_in=None, B, max_iter, rtol, iters_per_launch=None, stats=None):
+    """pidm_darcy_gen_acc, or pidm_darcy_gen_periodic for a periodic problem (same arguments, same state): launches of at most
+    `iters_per_launch` iterations per sample until every sample is done; the B done flags are read back after each launch.  A
+    batch larger than the device's compute units runs its workgroups one behind the other, so the budget of a launch is divided by
+    ceil(B / compute units)."""
     P = prob.P
     name = "pidm_darcy_gen_periodic" if prob.periodic else "pidm_darcy_gen_acc"
     entry = getattr(lib, name)
@@ -282,13 +263,13 @@ def _launch_acc(lib, device, prob, *, basis=None, z=None, K_in=None, B, max_iter
 
 def generate_darcy_batch(seeds, pixels_per_dim=64, q=64, length_scale=0.1, pixels_at_boundary=True, reverse_dy=True,
                          domain_length=1., basis=None, max_iter=None, rtol=RTOL, cache_dir=None, device=None, lib=None, acc=2,
-                         iters_per_launch=None, resumable=False, stats=None, bcs='none'):
+                         iters_per_launch=None, stats=None, bcs='none'):
     """Samples for the given seeds: K = exp(KLE(z(seed))) and the reference's least-squares pressure p at finite-difference order
     `acc` (2, 4 or 6).  Returns (K [B,P*P], p [B,P*P], res [B], iters [B]) on the device, fp64 (res = mean |row residual| over all
     P^2+4P+1 rows).  `basis` ([q, P*P], see kle_basis) overrides the eigendecomposition.  max_iter=None: MAX_ITER_ACC[acc].
-    acc 4 and 6 (and acc 2 with resumable=True) run in launches of at most `iters_per_launch` iterations (None: ITERS_PER_LAUNCH,
-    scaled to the batch); `stats` (a dict) receives the number of launches and the longest one.  bcs='periodic': the periodic system
-    (wrapped central operators, always in such launches) on fields of the periodic kle_basis."""
+    The solve runs in launches of at most `iters_per_launch` iterations (None: ITERS_PER_LAUNCH, scaled to the batch); `stats` (a
+    dict) receives `launches`, `longest_launch_s` and `iters_per_launch`.  bcs='periodic': the periodic system (wrapped central
+    operators) on fields of the periodic kle_basis."""
     device, lib = _resolve(device, lib)
     P = pixels_per_dim
     prob = DarcyProblem(P, pixels_at_boundary, reverse_dy, domain_length, acc, bcs)
@@ -303,7 +284,7 @@ def generate_darcy_batch(seeds, pixels_per_dim=64, q=64, length_scale=0.1, pixel
     z = torch.from_numpy(np.stack([z_of_seed(s, q) for s in seeds]) if seeds else np.zeros((0, q))).to(device)
     bt = torch.from_numpy(basis).to(device)
     K, p, res, iters, relres = _launch(lib, device, prob, basis=bt, z=z.contiguous(), B=len(seeds), max_iter=max_iter, rtol=rtol,
-                                       iters_per_launch=iters_per_launch, resumable=resumable, stats=stats)
+                                       iters_per_launch=iters_per_launch, stats=stats)
     if device.type == "cuda":
         torch.cuda.synchronize(device)
     _check_converged(relres.cpu().numpy(), rtol, [f"#{i} (seed {s})" for i, s in enumerate(seeds)])
@@ -311,10 +292,10 @@ def generate_darcy_batch(seeds, pixels_per_dim=64, q=64, length_scale=0.1, pixel
 
 
 def solve_darcy_pressure(K, pixels_at_boundary=True, reverse_dy=True, domain_length=1., max_iter=None, rtol=RTOL, lib=None,
-                         return_iters=False, acc=2, iters_per_launch=None, resumable=False, bcs='none'):
+                         return_iters=False, acc=2, iters_per_launch=None, bcs='none'):
     """The reference's least-squares pressure for given permeability fields K ([B,P,P] or [P,P], fp64 on the device) at
     finite-difference order `acc`.  Returns (p shaped like K, res [B]) - and iters [B] with return_iters.  max_iter,
-    iters_per_launch, resumable, bcs: see generate_darcy_batch."""
+    iters_per_launch, bcs: see generate_darcy_batch."""
     if not isinstance(K, torch.Tensor):
         raise PidmError("solve_darcy_pressure: K must be a torch tensor on the device")
     if lib is None and not K.is_cuda:
@@ -330,7 +311,7 @@ def solve_darcy_pressure(K, pixels_at_boundary=True, reverse_dy=True, domain_len
     max_iter = MAX_ITER_ACC[acc] if max_iter is None else max_iter
     Kin = K.to(torch.float64).reshape(B, P * P).contiguous()
     _, p, res, iters, relres = _launch(lib, K.device, prob, K_in=Kin, B=B, max_iter=max_iter, rtol=rtol,
-                                       iters_per_launch=iters_per_launch, resumable=resumable)
+                                       iters_per_launch=iters_per_launch)
     if K.is_cuda:
         torch.cuda.synchronize(K.device)
     _check_converged(relres.cpu().numpy(), rtol, [f"#{i}" for i in range(B)])
@@ -353,8 +334,7 @@ def _unique_seeds(n, seed=None):
 
 def generate_darcy_dataset(n_samples, out_dir, seed=None, seeds=None, batch=256, pixels_per_dim=64, q=64, length_scale=0.1,
                            pixels_at_boundary=True, reverse_dy=True, domain_length=1., max_iter=None, rtol=RTOL,
-                           cache_dir=None, device=None, lib=None, verbose=False, acc=2, iters_per_launch=None, resumable=False,
-                           bcs='none'):
+                           cache_dir=None, device=None, lib=None, verbose=False, acc=2, iters_per_launch=None, bcs='none'):
     """Writes out_dir/{seeds,K_data,p_data,res_data}.csv exactly as the reference main() (no header, no index, one row per
     sample) plus kle_basis.npy (the scaled basis the seeds were expanded in: a seed fixes K only together with it).
     `seeds` (explicit, must be distinct) or `seed` (draws n_samples distinct seeds reproducibly); neither: fresh ones.
@@ -379,7 +359,7 @@ def generate_darcy_dataset(n_samples, out_dir, seed=None, seeds=None, batch=256,
     for lo in range(0, n_samples, batch):
         K, p, res, iters = generate_darcy_batch(seeds[lo:lo + batch], P, q, length_scale, pixels_at_boundary, reverse_dy,
                                                 domain_length, basis=basis, max_iter=max_iter, rtol=rtol, device=device, lib=lib,
-                                                acc=acc, iters_per_launch=iters_per_launch, resumable=resumable, bcs=bcs)
+                                                acc=acc, iters_per_launch=iters_per_launch, bcs=bcs)
         Ks.append(K.cpu().numpy())
         ps.append(p.cpu().numpy())
         rs.append(res.cpu().numpy())
@@ -427,7 +407,7 @@ def main(argv=None):
     ap.add_argument("--bcs", default="none", choices=BCS, help="boundary conditions of the system and the fields (the model's bcs)")
     ap.add_argument("--max-iter", type=int, default=None, help="default: MAX_ITER_ACC of the order")
     ap.add_argument("--iters-per-launch", type=int, default=None,
-                    help="acc 4 / 6, periodic: CGLS iterations per kernel launch for a batch of one workgroup per compute unit")
+                    help="CGLS iterations per kernel launch for a batch of one workgroup per compute unit")
     ap.add_argument("--rtol", type=float, default=RTOL)
     ap.add_argument("--cache-dir", default=None, help="where the KLE basis is cached (default: not cached)")
     a = ap.parse_args(argv)

@@ -1,5 +1,6 @@
-"""Darcy training-data generation (csrc/k_darcy_gen.hip, physicsinformeddiffusionmodels_amd/darcy_data_generation.py) against a
-dense float64 least-squares oracle, the reference generator's golden samples (g25) and the engine's own training residual."""
+"""Darcy training-data generation at the default order 2 (csrc/k_darcy_gen_cgls.h with the operators of csrc/k_darcy_gen_acc.hip,
+physicsinformeddiffusionmodels_amd/darcy_data_generation.py) against a dense float64 least-squares oracle, the reference
+generator's golden samples (g25) and the engine's own training residual."""
 import functools
 import os
 
@@ -119,6 +120,22 @@ def test_batch_invariance(backend):
     assert torch.equal(Kb[7], K1[0]) and torch.equal(pb[7], p1[0])
 
 
+def test_launch_stats_and_split_invariance(backend):
+    """A default (acc=2) call reports its launches; cut into launches of 50 iterations it takes several and returns the same bits."""
+    lib, dev = _emu_or_gpu(backend)
+    P = 8
+    basis = D.kle_basis(P, 0.1, 64, True)
+    seeds = [5, 6, 7]
+    one, cut = {}, {}
+    ref = D.generate_darcy_batch(seeds, P, basis=basis, device=dev, lib=lib, stats=one)
+    out = D.generate_darcy_batch(seeds, P, basis=basis, device=dev, lib=lib, stats=cut, iters_per_launch=50)
+    assert one["launches"] >= 1 and isinstance(one["longest_launch_s"], float) and one["longest_launch_s"] > 0
+    assert isinstance(one["iters_per_launch"], int)
+    assert cut["launches"] > 1 and cut["iters_per_launch"] == 50
+    for a, b in zip(ref, out):
+        assert torch.equal(a, b)
+
+
 @pytest.mark.gpu
 def test_dataset_round_trip_into_training(tmp_path):
     import pandas as pd
@@ -168,10 +185,14 @@ def test_errors(backend, tmp_path):
     from physicsinformeddiffusionmodels_amd._lib import ptr, stream_ptr
     L = lib or __import__("physicsinformeddiffusionmodels_amd._lib", fromlist=["get_lib"]).get_lib()
     zz = torch.zeros(1, P * P + 1, dtype=torch.float64, device=dev)
-    assert L.pidm_darcy_gen(ptr(f), ptr(zz), P * P + 1, None, P, 0.1, 0.1, 1.0, ptr(f), ptr(f), 10, 1e-10, ptr(out), ptr(out),
-                            None, None, None, 1, stream_ptr(dev)) != 0
-    assert L.pidm_darcy_gen(None, None, 0, ptr(out), 128, 0.1, 0.1, 1.0, ptr(f), ptr(f), 10, 1e-10, None, ptr(out),
-                            None, None, None, 1, stream_ptr(dev)) != 0
+    done = torch.zeros(1, dtype=torch.int32, device=dev)
+    state = torch.zeros(L.pidm_darcy_gen_acc_state_bytes(P, 1) // 8, dtype=torch.float64, device=dev)
+    assert L.pidm_darcy_gen_acc(ptr(f), ptr(zz), P * P + 1, None, P, 2, 0.1, 0.1, 1.0, ptr(f), ptr(f), 10, 1e-10, 10, 1, ptr(state),
+                                ptr(out), ptr(out), None, None, None, ptr(done), 1, stream_ptr(dev)) != 0
+    assert b"darcy_gen_acc" in L.pidm_last_error() and b"q=" in L.pidm_last_error()
+    assert L.pidm_darcy_gen_acc(None, None, 0, ptr(out), 128, 2, 0.1, 0.1, 1.0, ptr(f), ptr(f), 10, 1e-10, 10, 1, ptr(state),
+                                None, ptr(out), None, None, None, ptr(done), 1, stream_ptr(dev)) != 0
+    assert b"darcy_gen_acc" in L.pidm_last_error() and b"P=128" in L.pidm_last_error()
 
 
 def test_product_library_rejects_cpu_tensors():

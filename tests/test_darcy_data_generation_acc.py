@@ -1,7 +1,7 @@
-"""Darcy training-data generation at finite-difference orders 4 and 6 (csrc/k_darcy_gen_acc.hip, the `acc` keyword of
+"""Darcy training-data generation with findiff's classed operators of every order (csrc/k_darcy_gen_acc.hip, the `acc` keyword of
 physicsinformeddiffusionmodels_amd/darcy_data_generation.py) against a dense float64 least-squares oracle built from
-grad_utils.fd_coefficients, the reference generator's golden samples (g28), the second-order kernel, the launch-split protocol and
-the engine's own training residual at the same order."""
+grad_utils.fd_coefficients, the reference generator's golden samples (g28), the launch-split protocol and the engine's own
+training residual at the same order."""
 import functools
 import os
 
@@ -92,24 +92,14 @@ def test_split_invariance(backend):
         assert torch.equal(r, r1)
 
 
-# ---- 4. second order through the new entry --------------------------------------------------------------------------------------------
+# ---- 4. second order ------------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("P", [8, 16])
-def test_resumable_acc2_matches_second_order_kernel(backend, P):
-    lib, dev = _emu_or_gpu(backend)
-    K = torch.from_numpy(np.stack([_field(P, True, 11 + P), _field(P, True, 977)])).to(dev)
-    pref, rref = D.solve_darcy_pressure(K, lib=lib)
-    p, r = D.solve_darcy_pressure(K, lib=lib, acc=2, resumable=True, iters_per_launch=300)
-    for s in range(2):
-        assert float((p[s] - pref[s]).abs().max()) <= TOL * float(pref[s].abs().max())
-        assert abs(float(r[s]) - float(rref[s])) <= TOL * float(rref[s])
-
-
 @pytest.mark.parametrize("pab,rev", CASES)
-def test_resumable_acc2_matches_dense_lstsq(backend, pab, rev):
-    """The classed instantiation of order 2 against the dense oracle at the smallest grid the entry accepts (the edge classes touch
-    the central band), cut into launches of 300 iterations."""
-    _dense_case(*_emu_or_gpu(backend), 8, pab, rev, 2, resumable=True, iters_per_launch=300)
+def test_acc2_matches_dense_lstsq(backend, P, pab, rev):
+    """The classed instantiation of order 2 against the dense oracle built from grad_utils.fd_coefficients, at the smallest grid the
+    entry accepts (the edge classes touch the central band) and at P = 16, cut into launches of 300 iterations."""
+    _dense_case(*_emu_or_gpu(backend), P, pab, rev, 2, iters_per_launch=300)
 
 
 # ---- 5. batch invariance ----------------------------------------------------------------------------------------------------------------

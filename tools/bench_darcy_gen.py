@@ -1,11 +1,11 @@
-"""Throughput of the Darcy data generator (csrc/k_darcy_gen.hip) on the MI355X: samples/s and CGLS iterations per sample
-(min / median / max) at P = 64 for batches of 256 and 1024, and at P = 32.  The KLE basis (host eigh) is computed once per P
-and not timed.  --acc 4 / 6 (csrc/k_darcy_gen_acc.hip) and --resumable (acc 2 through the same entry) also report the number of
-launches and the longest single launch (launch + read-back of the done flags).  --bcs periodic (csrc/k_darcy_gen_per.hip) solves
-the periodic system on fields of the periodic KLE basis, through the same launches (both files instantiate the solver body of
-csrc/k_darcy_gen_cgls.h).  Results go to stdout; DESIGN.md / profiles/ keep the recorded numbers.
+"""Throughput of the Darcy data generator (csrc/k_darcy_gen_cgls.h) on the MI355X: samples/s and CGLS iterations per sample
+(min / median / max) at P = 64 for batches of 256 and 1024, and at P = 32, with the number of launches and the longest single
+launch (launch + read-back of the done flags).  The KLE basis (host eigh) is computed once per P and not timed.  --acc 2 / 4 / 6
+selects the classed operators (csrc/k_darcy_gen_acc.hip); --bcs periodic (csrc/k_darcy_gen_per.hip) solves the periodic system on
+fields of the periodic KLE basis (both files instantiate the one solver body).  Results go to stdout; DESIGN.md / profiles/ keep
+the recorded numbers.
 
-    python tools/bench_darcy_gen.py [--cases 64:256,64:1024,32:256] [--acc 4] [--iters-per-launch N] [--resumable] [--bcs periodic]
+    python tools/bench_darcy_gen.py [--cases 64:256,64:1024,32:256] [--acc 4] [--iters-per-launch N] [--bcs periodic]
 """
 import argparse
 import os
@@ -24,11 +24,10 @@ def main():
     ap.add_argument("--cases", default="64:256,64:1024,32:256")
     ap.add_argument("--acc", type=int, default=2, choices=D.ACCS)
     ap.add_argument("--iters-per-launch", type=int, default=None)
-    ap.add_argument("--resumable", action="store_true", help="acc 2 through the resumable entry")
     ap.add_argument("--max-iter", type=int, default=None)
     ap.add_argument("--bcs", default="none", choices=D.BCS)
     a = ap.parse_args()
-    kw = dict(acc=a.acc, iters_per_launch=a.iters_per_launch, resumable=a.resumable, max_iter=a.max_iter, bcs=a.bcs)
+    kw = dict(acc=a.acc, iters_per_launch=a.iters_per_launch, max_iter=a.max_iter, bcs=a.bcs)
     dev = torch.device("cuda:0")
     bases = {}
     for case in a.cases.split(","):
@@ -45,9 +44,8 @@ def main():
         torch.cuda.synchronize()
         dt = time.perf_counter() - t
         it = iters.cpu().numpy()
-        entry = "pidm_darcy_gen" if st["longest_launch_s"] is None else (
-            f"{'pidm_darcy_gen_periodic' if a.bcs == 'periodic' else 'pidm_darcy_gen_acc'}, {st['launches']} launches of <= {st['iters_per_launch']} iterations, longest "
-            f"{st['longest_launch_s']:.3f} s")
+        entry = (f"{'pidm_darcy_gen_periodic' if a.bcs == 'periodic' else 'pidm_darcy_gen_acc'}, {st['launches']} launches of <= "
+                 f"{st['iters_per_launch']} iterations, longest {st['longest_launch_s']:.3f} s")
         print(f"P={P} B={B} acc={a.acc} bcs={a.bcs} ({entry}): {dt:.3f} s, {B / dt:.1f} samples/s, iterations min {it.min()} median {int(np.median(it))} "
               f"max {it.max()}, {dt / B * 1e3:.2f} ms/sample, {dt / it.max() * 1e6:.2f} us per iteration of the batch, "
               f"res {float(res.mean()):.3e}", flush=True)
