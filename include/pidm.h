@@ -154,6 +154,33 @@ int pidm_darcy_guidance_cotangent(const float* x0_pred, const float* obs, const 
 int pidm_guidance_scale_general(const float* x0_pred, const float* obs, const float* mask, const float* residual, float zeta_obs,
                                 float zeta_pde, float* grad_res, float* v_obs, float* sums, int B, int P, void* stream);
 int pidm_guidance_add(float* v, const float* adjoint, size_t n, void* stream);
+/* Flux observations.  The Darcy flux of a sample is q = (q0, q1) = (-K D0 p, -K D1 p) [B,2,P,P] with D0 / D1 the residual's own
+ * first-derivative operators (order fd_acc, classed or periodic, spacing d0 / d1).  With readings y_q under a 0/1 mask m_q
+ * (both [B,2,P,P]): L_flux = sum m_q (q - y_q)^2 and Phi gains zeta_flux sqrt(L_flux); with e_c = m_q,c (q_c - y_q,c) and
+ * s_f = zeta_flux / sqrt(L_flux) the new part of v is  v_p += s_f sum_c D_c^T (-K e_c),  v_K += s_f (-sum_c e_c D_c p)
+ * (omitted, like the other terms, when L_flux is exactly 0).
+ *
+ * pidm_darcy_flux: q of x0 for any stencil set.  ops2_host = the operators d/d0, d/d1.  One two-operator stencil launch on p and
+ * one pointwise kernel.  workspace: >= pidm_darcy_flux_ws(B, P) bytes; on return it holds D0 p [B,P*P] followed by D1 p [B,P*P]. */
+size_t pidm_darcy_flux_ws(int B, int P);
+int pidm_darcy_flux(const float* x0, const pidm_stencil_op* ops2_host, int periodic, float* flux, void* workspace, int B, int P,
+                    void* stream);
+/* pidm_darcy_guidance_cotangent with the flux term: second-order, non-periodic stencils, v and sums [B,3] = (L_obs, L_pde, L_flux)
+ * in ONE launch.  Same LDS plan (8 P^2 floats), so the same 5 <= P <= 71: the sums are taken in a first pass that stores nothing,
+ * a second pass rebuilds the stencil values from the resident sample and stores the adjoint operands already scaled, flux part
+ * included; anything else fails with a message. */
+int pidm_darcy_guidance_cotangent_flux(const float* x0_pred, const float* obs, const float* mask, const float* flux_obs,
+                                       const float* flux_mask, const float* f_s, float inv_h0, float inv_h1, float zeta_obs,
+                                       float zeta_pde, float zeta_flux, float* v, float* sums, int B, int P, void* stream);
+/* Any stencil set, any P: the flux term on top of the composition above, after pidm_guidance_add.  dp0 / dp1 [B,P*P] = D0 p, D1 p
+ * (the first two fields pidm_darcy_residual_general_fwd / _bwd leave in their workspace, or the workspace of pidm_darcy_flux / one
+ * pidm_stencil_apply on p).  Writes sums3 [B,3] = (sums2[b,0], sums2[b,1], L_flux) (sums2 [B,2] may be NULL: only the flux slot is
+ * written), w [B,2,P,P] = s_f (-K e_c), and the K channel v_out = v_in + s_f (-sum_c e_c D_c p) (v_out == v_in is allowed).  The
+ * p channel is then ONE pidm_stencil_apply_adjoint of (d/d0, d/d1) over w with add = the p channel of v_in, gx = that of v_out
+ * (distinct buffers). */
+int pidm_guidance_flux_general(const float* x0_pred, const float* dp0, const float* dp1, const float* flux_obs, const float* flux_mask,
+                               float zeta_flux, const float* sums2, float* sums3, float* w, const float* v_in, float* v_out, int B,
+                               int P, void* stream);
 /* guided ancestral update x_{t-1} = c1 x0_pred + c2 x_t + sigma z - g; g [B,HW,C] is the UNet's input-gradient layout
  * (pidm_unet_backward_input), read transposed; everything else [B,C,HW].  C <= 16. */
 int pidm_psample_update_guided(const float* x0_pred, const float* x_t, const float* z, const float* g_nhwc, float c1, float c2,

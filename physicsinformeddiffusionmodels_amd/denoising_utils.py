@@ -958,7 +958,8 @@ class DenoisingDiffusion(nn.Module):
         return x_seq, interm_imgs
 
     def p_sample_loop_guided(self, shape, residual_func, obs, mask, zeta_obs=1.0, zeta_pde=0.0, guide_below=None,
-                             surpress_noise=True, replace_observed=False, keep_history=True):
+                             surpress_noise=True, replace_observed=False, keep_history=True, flux_obs=None, flux_mask=None,
+                             zeta_flux=0.0):
         """Conditional Darcy sampling by posterior guidance (an extension: the reference has no counterpart).
 
         obs, mask: [B,2,P,P] or broadcastable [1,2,P,P]; channel 0 is p, channel 1 is K; the mask is 0/1.  K fully observed = the
@@ -969,12 +970,18 @@ class DenoisingDiffusion(nn.Module):
         (four native calls; no weight gradient is computed and no gradient state of the model is touched).  Steps at or above
         `guide_below` are plain `p_sample` arithmetic.  `replace_observed=True` writes `obs` into the masked entries of the final state.
 
-        zeta_obs / zeta_pde are user parameters.  Their defaults are PLACEHOLDERS: no trained checkpoint was available when this was
-        written, the right magnitudes depend on the model and the schedule, and nothing here claims sample quality.
+        flux_obs, flux_mask (given together, [B,2,P,P] or [1,2,P,P]): readings of the Darcy flux q = (-K d0 p, -K d1 p) of the
+        x0 estimate (`ResidualsDarcy.flux_of`: flow meters, tracer velocities) under a 0/1 mask; Phi gains
+        zeta_flux sqrt(sum flux_mask (q(x0_hat) - flux_obs)^2).  The flux is not a state variable: `replace_observed` does not
+        touch it.
+
+        zeta_obs / zeta_pde / zeta_flux are user parameters.  Their defaults are PLACEHOLDERS: no trained checkpoint was available when
+        this was written, the right magnitudes depend on the model and the schedule, and nothing here claims sample quality.
 
         Returns `((x_seq, interm), aux)` like `p_sample_loop(..., eval_residuals=True)`: aux['residual'] [B] = per-sample mean |r| of
         the final state, aux['guidance'] [n_steps,B,2] = (L_obs, L_pde) of the x0 estimate per step in the order the steps are
-        taken (zeros for unguided steps), kept on the device - nothing is read back inside the loop."""
+        taken (zeros for unguided steps), kept on the device - nothing is read back inside the loop.  With flux data it is
+        [n_steps,B,3] = (L_obs, L_pde, L_flux)."""
         from ._engine import frozen_weights, input_gradient_pass
         from ._lib import PidmError
         if residual_func is None or getattr(residual_func, 'gov_eqs', None) != 'darcy':
@@ -992,12 +999,23 @@ class DenoisingDiffusion(nn.Module):
             if not torch.is_tensor(a) or a.dim() != 4 or tuple(a.shape[1:]) != shape[1:] or a.shape[0] not in (1, B):
                 raise PidmError(f"p_sample_loop_guided: {name} must be [B,2,P,P] or [1,2,P,P] for shape {shape}, got "
                                 f"{tuple(a.shape) if torch.is_tensor(a) else type(a).__name__}")
+        with_flux = flux_obs is not None or flux_mask is not None
+        if with_flux:
+            for name, a in (('flux_obs', flux_obs), ('flux_mask', flux_mask)):
+                if not torch.is_tensor(a) or a.dim() != 4 or tuple(a.shape[1:]) != shape[1:] or a.shape[0] not in (1, B):
+                    raise PidmError(f"p_sample_loop_guided: {name} must be [B,2,P,P] or [1,2,P,P] for shape {shape} (flux_obs and "
+                                    f"flux_mask are given together), got {tuple(a.shape) if torch.is_tensor(a) else type(a).__name__}")
         dev = self.diff_dict['alphas'].device
         obs_d = obs.detach().to(device=dev, dtype=torch.float32).expand(shape).contiguous()
         mask_d = mask.detach().to(device=dev, dtype=torch.float32).expand(shape).contiguous()
         guide_below = self.n_steps if guide_below is None else int(guide_below)
         lib, ht = self.lib, self._host_tables
-        guidance = torch.zeros(self.n_steps, B, 2, dtype=torch.float32, device=dev)
+        flux_kw = {}
+        if with_flux:
+            flux_kw = dict(flux_obs=flux_obs.detach().to(device=dev, dtype=torch.float32).expand(shape).contiguous(),
+                           flux_mask=flux_mask.detach().to(device=dev, dtype=torch.float32).expand(shape).contiguous(),
+                           zeta_flux=zeta_flux)
+        guidance = torch.zeros(self.n_steps, B, 3 if with_flux else 2, dtype=torch.float32, device=dev)
         cur_x = torch.randn(shape, device=dev)
         x_seq = [cur_x.detach().cpu()] if keep_history else []
         interm = [torch.zeros(shape)] if keep_history else []     # (as p_sample_loop(save_output=True): no estimate before the first step)
@@ -1010,7 +1028,7 @@ class DenoisingDiffusion(nn.Module):
                 out = torch.empty_like(xi)
                 if i < guide_below:
                     x0p, pull = input_gradient_pass(net, xi, tt)
-                    v, _ = residual_func.guidance_cotangent(x0p, obs_d, mask_d, zeta_obs, zeta_pde, sums_out=guidance[k])
+                    v, _ = residual_func.guidance_cotangent(x0p, obs_d, mask_d, zeta_obs, zeta_pde, sums_out=guidance[k], **flux_kw)
                     g = pull(v)
                     z = torch.randn_like(xi)
                     lib.check(lib.pidm_psample_update_guided(ptr(x0p), ptr(xi), ptr(z), ptr(g), c1, c2, sigma, ptr(out), B, 2, P * P,

@@ -11,6 +11,8 @@ forward, the pointwise adjoint and two adjoint launches backward.
 """
 from __future__ import annotations
 
+import ctypes as C
+
 import torch
 
 from ._lib import PidmError, get_lib, ptr, stream_ptr
@@ -156,17 +158,54 @@ class ResidualsDarcy:
         return _DarcyResidualGeneralFn.apply(x0_pred, self._f_s_flat, (sg.d_d0, sg.d_d1, sg.d_d00, sg.d_d11), self.periodic,
                                              1.0 if self.reverse_d1 else -1.0, self.lib)
 
-    def guidance_cotangent(self, x0_pred, obs, mask, zeta_obs, zeta_pde, sums_out=None):
+    def _first_derivative_ops(self, P, rows=None):
+        sg = self.grads.stencil_gradients
+        need = max(sg.d_d0.min_size(), sg.d_d1.min_size())
+        if (rows is not None and rows != P) or P < need:
+            raise ValueError(f'a {P if rows is None else rows} x {P} field does not fit the fd_acc={self.fd_acc} stencils (square, >= {need})')
+        return sg.d_d0, sg.d_d1
+
+    def flux_of(self, x0):
+        """Darcy flux q = (-K D0 p, -K D1 p) of samples x0 [B,2,P,P] -> [B,2,P,P] on the device, with the first-derivative operators
+        of this instance's residual (order `fd_acc`, classed or periodic, spacing d0 / d1, d1 negative under `reverse_d1`): the
+        node-centred flux.  One two-operator stencil launch on p and one pointwise kernel.  Forward only: the input is detached."""
+        if x0.dim() != 4 or x0.shape[1] != 2:
+            raise AssertionError('Model output must be a tensor shaped as an image [B,2,P,P].')
+        if self._lib is None and not x0.is_cuda:
+            raise PidmError('ResidualsDarcy needs tensors on an MI355X: the gfx950 kernels have no CPU fallback')
+        comps = self._first_derivative_ops(x0.shape[-1], x0.shape[-2])
+        lib, dev = self.lib, x0.device
+        x = x0.detach().contiguous().float()
+        B, _, P, _ = x.shape
+        q = torch.empty_like(x)
+        ws = torch.empty(lib.pidm_darcy_flux_ws(B, P), dtype=torch.uint8, device=dev)
+        ops, keep = _ops_array(comps, dev)
+        lib.check(lib.pidm_darcy_flux(ptr(x), ops, int(self.periodic), ptr(q), ptr(ws), B, P, stream_ptr(dev)), 'pidm_darcy_flux')
+        return q
+
+    def guidance_cotangent(self, x0_pred, obs, mask, zeta_obs, zeta_pde, sums_out=None, flux_obs=None, flux_mask=None, zeta_flux=0.0):
         """Posterior-guidance cotangent of an x0 estimate (csrc/k_guidance.hip).  x0_pred, obs, mask: [B,2,P,P] (mask 0/1).
         Per sample Phi = zeta_obs sqrt(L_obs) + zeta_pde sqrt(L_pde) with L_obs = sum mask (x0_pred - obs)^2 and L_pde = sum r^2;
         returns `(v, sums)`: v = dPhi/dx0_pred [B,2,P,P] and sums [B,2] = (L_obs, L_pde).  A term whose L is exactly 0 is omitted.
         The second-order non-periodic configuration is one launch; the general stencil sets run residual -> scale -> adjoint ->
-        add on the device.  `sums_out`: a contiguous [B,2] fp32 tensor to write the sums into (no allocation, no copy)."""
+        add on the device.  `sums_out`: a contiguous [B,2] fp32 tensor to write the sums into (no allocation, no copy).
+
+        `flux_obs`, `flux_mask` [B,2,P,P] (given together): readings of the flux q = `flux_of(x0_pred)` under a 0/1 mask.  Phi gains
+        zeta_flux sqrt(L_flux) with L_flux = sum flux_mask (q - flux_obs)^2, and sums (and `sums_out`) are [B,3] = (L_obs, L_pde,
+        L_flux).  Still one launch where the one-launch kernel applies; otherwise the composition above plus at most three launches
+        (derivatives of p where the residual did not leave them, the pointwise flux kernel, one stencil adjoint)."""
         if x0_pred.dim() != 4 or x0_pred.shape[1] != 2 or x0_pred.shape[-1] != x0_pred.shape[-2]:
             raise PidmError(f'guidance_cotangent: x0_pred must be [B,2,P,P], got {tuple(x0_pred.shape)}')
         if tuple(obs.shape) != tuple(x0_pred.shape) or tuple(mask.shape) != tuple(x0_pred.shape):
             raise PidmError(f'guidance_cotangent: obs {tuple(obs.shape)} / mask {tuple(mask.shape)} must match x0_pred '
                             f'{tuple(x0_pred.shape)}')
+        with_flux = flux_obs is not None or flux_mask is not None
+        if with_flux:
+            if flux_obs is None or flux_mask is None:
+                raise PidmError('guidance_cotangent: flux_obs and flux_mask must be given together')
+            if tuple(flux_obs.shape) != tuple(x0_pred.shape) or tuple(flux_mask.shape) != tuple(x0_pred.shape):
+                raise PidmError(f'guidance_cotangent: flux_obs {tuple(flux_obs.shape)} / flux_mask {tuple(flux_mask.shape)} must match '
+                                f'x0_pred {tuple(x0_pred.shape)}')
         if self._lib is None and not x0_pred.is_cuda:
             raise PidmError('ResidualsDarcy needs tensors on an MI355X: the gfx950 kernels have no CPU fallback')
         lib, dev = self.lib, x0_pred.device
@@ -177,13 +216,23 @@ class ResidualsDarcy:
         if self._f_s_flat.device != dev:
             self._f_s_flat = self._f_s_flat.to(dev)
         v = torch.empty_like(x)
-        sums = sums_out if sums_out is not None else torch.empty(B, 2, dtype=torch.float32, device=dev)
-        if tuple(sums.shape) != (B, 2) or sums.dtype != torch.float32 or not sums.is_contiguous() or sums.device != dev:
-            raise PidmError('guidance_cotangent: sums_out must be a contiguous fp32 [B,2] tensor on the input device')
+        ns = 3 if with_flux else 2
+        sums = sums_out if sums_out is not None else torch.empty(B, ns, dtype=torch.float32, device=dev)
+        if tuple(sums.shape) != (B, ns) or sums.dtype != torch.float32 or not sums.is_contiguous() or sums.device != dev:
+            raise PidmError(f'guidance_cotangent: sums_out must be a contiguous fp32 [B,{ns}] tensor on the input device')
         st = stream_ptr(dev)
-        # the one-launch kernel keeps a sample and its six adjoint operands in LDS (8 P^2 floats of the 160 KiB); larger fields take
+        if with_flux:
+            yq = flux_obs.detach().to(dev).contiguous().float()
+            mq = flux_mask.detach().to(dev).contiguous().float()
+        # the one-launch kernels keep a sample and its six adjoint operands in LDS (8 P^2 floats of the 160 KiB); larger fields take
         # the composition below on the second-order residual kernels
         if self.specialised and 8 * P * P * 4 <= 160 * 1024 - 256:
+            if with_flux:
+                lib.check(lib.pidm_darcy_guidance_cotangent_flux(ptr(x), ptr(y), ptr(m), ptr(yq), ptr(mq), ptr(self._f_s_flat),
+                                                                 self.inv_h0, self.inv_h1, float(zeta_obs), float(zeta_pde),
+                                                                 float(zeta_flux), ptr(v), ptr(sums), B, P, st),
+                          'pidm_darcy_guidance_cotangent_flux')
+                return v, sums
             lib.check(lib.pidm_darcy_guidance_cotangent(ptr(x), ptr(y), ptr(m), ptr(self._f_s_flat), self.inv_h0, self.inv_h1,
                                                         float(zeta_obs), float(zeta_pde), ptr(v), ptr(sums), B, P, st),
                       'pidm_darcy_guidance_cotangent')
@@ -191,6 +240,8 @@ class ResidualsDarcy:
         res = torch.empty(B, P * P, 3, dtype=torch.float32, device=dev)
         gres = torch.empty_like(res)
         adj = torch.empty_like(x)
+        sums2 = torch.empty(B, 2, dtype=torch.float32, device=dev) if with_flux else sums
+        dp = None           # (D0 p, D1 p) [B,P*P] each, where the residual leaves them behind
         if self.specialised:
             fwd = lambda: lib.check(lib.pidm_darcy_residual_fwd(ptr(x), ptr(self._f_s_flat), self.inv_h0, self.inv_h1, ptr(res), B, P, st),
                                     'pidm_darcy_residual_fwd')
@@ -208,12 +259,32 @@ class ResidualsDarcy:
                                                                         ptr(res), ptr(ws), B, P, st), 'pidm_darcy_residual_general_fwd')
             bwd = lambda: lib.check(lib.pidm_darcy_residual_general_bwd(ptr(x), ptr(gres), ops, int(self.periodic), bc1_sign, ptr(adj),
                                                                         ptr(ws), B, P, st), 'pidm_darcy_residual_general_bwd')
+            dp = ws.view(torch.float32)[:2 * B * P * P]         # the workspace starts with the fields p_0, p_1 [B,P*P]
         fwd()
         lib.check(lib.pidm_guidance_scale_general(ptr(x), ptr(y), ptr(m), ptr(res), float(zeta_obs), float(zeta_pde), ptr(gres),
-                                                  ptr(v), ptr(sums), B, P, st), 'pidm_guidance_scale_general')
+                                                  ptr(v), ptr(sums2), B, P, st), 'pidm_guidance_scale_general')
         bwd()
         lib.check(lib.pidm_guidance_add(ptr(v), ptr(adj), v.numel(), st), 'pidm_guidance_add')
-        return v, sums
+        if not with_flux:
+            return v, sums
+        # flux term: [derivatives of p] -> pointwise kernel (L_flux, cotangents w, K channel) -> stencil adjoint (p channel).  The
+        # result goes into `adj`, which is free again: the adjoint's `add` and output are distinct buffers
+        comps = self._first_derivative_ops(P)
+        ops2, keep2 = _ops_array(comps, dev)
+        N = P * P
+        if dp is None:
+            dp = torch.empty(2 * B * N, dtype=torch.float32, device=dev)
+            outs = (C.c_void_p * 2)(dp.data_ptr(), dp.data_ptr() + 4 * B * N)
+            lib.check(lib.pidm_stencil_apply(ptr(x), 2 * N, ops2, outs, 2, N, B, P, P, int(self.periodic), st), 'pidm_stencil_apply')
+        w = gres.view(-1)[:2 * B * N]                           # (the scaled residual is consumed: its buffer takes the cotangents)
+        out = adj
+        lib.check(lib.pidm_guidance_flux_general(ptr(x), C.c_void_p(dp.data_ptr()), C.c_void_p(dp.data_ptr() + 4 * B * N), ptr(yq), ptr(mq),
+                                                 float(zeta_flux), ptr(sums2), ptr(sums), ptr(w), ptr(v), ptr(out), B, P, st),
+                  'pidm_guidance_flux_general')
+        gs = (C.c_void_p * 2)(w.data_ptr(), w.data_ptr() + 4 * N)
+        lib.check(lib.pidm_stencil_apply_adjoint(gs, 2 * N, ops2, 2, ptr(v), 2 * N, ptr(out), 2 * N, B, P, P, int(self.periodic), st),
+                  'pidm_stencil_apply_adjoint')
+        return out, sums
 
     def compute_residual(self, input, reduce='none', return_model_out=False, return_optimizer=False,
                          return_inequality=False, sample=False, ddim_func=None, pass_through=False):

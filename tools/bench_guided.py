@@ -3,7 +3,9 @@
   (b) training-mode forward + pidm_unet_backward with an input gradient - how an input gradient was obtained before
       pidm_unet_backward_input existed (weight gradients computed and thrown away),
   (c) input_gradient_pass + cotangent kernel + pull + guided update kernel - the step of p_sample_loop_guided;
-      (c-unet) is its UNet part alone (input_gradient_pass + pull), the like-for-like counterpart of (b).
+      (c-unet) is its UNet part alone (input_gradient_pass + pull), the like-for-like counterpart of (b),
+  (c-flux) the same step with flux readings (flux_obs / flux_mask / zeta_flux): the one-launch flux cotangent kernel in place of
+      the two-term one; its yardstick is (c) of the same run.
 The legs alternate inside every round; the median over the rounds is reported, with the kernels per step from
 pidm_debug_launch_counts (enqueued launch by launch + inside replayed graphs).  Usage: bench_guided.py [--out FILE] [BATCH ...]"""
 import ctypes as C
@@ -64,6 +66,8 @@ def main():
         obs = torch.randn(B, 2, P, P, generator=g).to(dev)
         obs[:, 1] = torch.exp(0.5 * obs[:, 1])
         mask = (torch.rand(B, 2, P, P, generator=g) < 0.1).float().to(dev)
+        yq = torch.randn(B, 2, P, P, generator=g).to(dev)
+        mq = (torch.rand(B, 2, P, P, generator=g) < 0.1).float().to(dev)
         t = torch.full((B,), 50, dtype=torch.long, device=dev)
         x_nhwc = x.permute(0, 2, 3, 1).reshape(B, P * P, 2).contiguous()
         out = torch.empty_like(x)
@@ -90,8 +94,16 @@ def main():
                 gr = pull(v)
                 L.check(L.pidm_psample_update_guided(ptr(x0p), ptr(x), ptr(z), ptr(gr), 0.3, 0.7, 0.05, ptr(out), B, 2, P * P, stream_ptr(dev)))
 
+        def leg_c_flux():
+            with torch.no_grad():
+                x0p, pull = input_gradient_pass(m, x_nhwc, t)
+                v, _ = res.guidance_cotangent(x0p, obs, mask, 1.0, 1e-3, flux_obs=yq, flux_mask=mq, zeta_flux=0.01)
+                gr = pull(v)
+                L.check(L.pidm_psample_update_guided(ptr(x0p), ptr(x), ptr(z), ptr(gr), 0.3, 0.7, 0.05, ptr(out), B, 2, P * P, stream_ptr(dev)))
+
         legs = [("a  inference forward", leg_a), ("b  training forward + full backward", leg_b),
-                ("c-unet  input_gradient_pass + pull", leg_c_unet), ("c  guided step (4 native calls)", leg_c)]
+                ("c-unet  input_gradient_pass + pull", leg_c_unet), ("c  guided step (4 native calls)", leg_c),
+                ("c-flux  guided step with flux readings", leg_c_flux)]
         times = {k: [] for k, _ in legs}
         count = {}
         with frozen_weights(m):
@@ -117,6 +129,8 @@ def main():
             lines.append(f"  ({k:42s}) {statistics.median(v):9.3f} ms  ({min(v):.3f} .. {max(v):.3f})  {count[k]:4d} kernels / step")
         b_, c_ = statistics.median(times[legs[1][0]]), statistics.median(times[legs[2][0]])
         lines.append(f"  c-unet / b = {c_ / b_:.3f}")
+        g_, f_ = statistics.median(times[legs[3][0]]), statistics.median(times[legs[4][0]])
+        lines.append(f"  c-flux / c = {f_ / g_:.4f}  (c-flux - c = {1e3 * (f_ - g_):+.1f} us)")
     text = "\n".join(lines) + "\n"
     print(text, end="")
     if out_path:
