@@ -623,6 +623,8 @@ __global__ void __launch_bounds__(256) floating_material_kernel(const float* __r
 using namespace pidm;
 
 extern "C" int pidm_bilinear_resize(const float* in, float* out, int BC, int Hi, int Ho, void* stream) {
+  if (!in || !out) return fail("bilinear_resize: null buffer");
+  if (BC <= 0 || Hi < 1 || Ho < 1) return fail("bilinear_resize: BC, Hi and Ho must be positive");
   size_t n = (size_t)BC * Ho * Ho;
   int blocks = (int)((n + 255) / 256);
   if (blocks > 4096) blocks = 4096;
@@ -642,8 +644,11 @@ extern "C" int pidm_mech_residual_fwd(const float* x0_pred, const float* bcs, co
                                       float* residual, float* model_out, float* comp_shift, int B, void* stream) {
   const int E = nel * nel, nn = nel + 1, ndof = 2 * nn * nn;
   if (mech_args(nel, E, ndof, kloc, elem_dofs, dof_elems)) return -1;
+  if (!x0_pred || !bcs || !vf || !residual || !model_out || !comp_shift) return fail("mech_residual_fwd: null buffer");
+  if (B <= 0) return fail("mech_residual_fwd: B must be positive");
   MechMesh ms{elem_dofs, dof_elems, kloc, kloc_stride, E, ndof, nel, nn};
   const size_t lds = (size_t)(ndof + E) * sizeof(float);
+  if (lds > 150 * 1024) return fail("mech: mesh does not fit LDS");
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mech_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
@@ -662,6 +667,8 @@ extern "C" int pidm_mech_residual_bwd(const float* x0_pred, const float* bcs, co
                                       void* stream) {
   const int E = nel * nel, nn = nel + 1, ndof = 2 * nn * nn;
   if (mech_args(nel, E, ndof, kloc, elem_dofs, dof_elems)) return -1;
+  if (!x0_pred || !bcs || !g_residual || !g_comp_shift || !g_x0_pred) return fail("mech_residual_bwd: null buffer");   // g_model_out may be null
+  if (B <= 0) return fail("mech_residual_bwd: B must be positive");
   MechMesh ms{elem_dofs, dof_elems, kloc, kloc_stride, E, ndof, nel, nn};
   const size_t lds = (size_t)(3 * ndof + E) * sizeof(float);
   if (lds > 150 * 1024) return fail("mech: mesh does not fit LDS");
@@ -712,6 +719,7 @@ extern "C" int pidm_mech_apply(const float* rho, const float* u_img, const float
   const int E = nel * nel, nn = nel + 1, ndof = 2 * nn * nn;
   if (mech_args(nel, E, ndof, kloc, elem_dofs, dof_elems)) return -1;
   if (!rho || !u_img || !bcs || !residual || !comp_uf) return fail("mech_apply: null buffer");
+  if (B <= 0) return fail("mech_apply: B must be positive");
   MechMesh ms{elem_dofs, dof_elems, kloc, kloc_stride, E, ndof, nel, nn};
   const size_t lds = (size_t)(ndof + E) * sizeof(float);
   if (lds > 150 * 1024) return fail("mech: mesh does not fit LDS");
@@ -736,6 +744,7 @@ extern "C" int pidm_mech_solve(const float* rho, const float* bcs, const float* 
   const int E = nel * nel, nn = nel + 1, ndof = 2 * nn * nn;
   if (mech_args(nel, E, ndof, kloc, elem_dofs, dof_elems)) return -1;
   if (!rho || !bcs || !compliance || !workspace) return fail("mech_solve: null buffer");
+  if (B <= 0) return fail("mech_solve: B must be positive");
   if (max_iter < 1 || !(rtol > 0.0)) return fail("mech_solve: max_iter >= 1 and rtol > 0 required");
   MechMesh ms{elem_dofs, dof_elems, kloc, kloc_stride, E, ndof, nel, nn};
   const size_t lds = (size_t)ndof * sizeof(double) + (size_t)E * sizeof(float);
@@ -754,6 +763,7 @@ extern "C" int pidm_mech_solve(const float* rho, const float* bcs, const float* 
 
 extern "C" int pidm_floating_material(const float* rho, float threshold, int nel, int32_t* n_components, int B, void* stream) {
   if (!rho || !n_components) return fail("floating_material: null buffer");
+  if (B <= 0) return fail("floating_material: B must be positive");
   const size_t lds = (size_t)nel * nel * sizeof(int);
   if (nel < 1 || lds > 150 * 1024) return fail("floating_material: nel=%d out of range", nel);
   static bool attr = false;
