@@ -49,6 +49,7 @@ long long pidm_prof_kernels_collect(char* buf, size_t cap);
  * x0      [B,2,P,P] NCHW (ch0 = pressure, ch1 = permeability) - the layout the reference UNet returns
  * residual[B,P*P,3]  (eq, bc0, bc1)
  * inv_h0 = 1/d0, inv_h1 = 1/d1 (d1 negative when reverse_d1).  f_s [P*P] source field.
+ * A null buffer, B <= 0, P < 5 or a P whose row bands do not fit LDS is refused before anything is launched (Darcy loss included).
  * ------------------------------------------------------------------------------------------- */
 int pidm_darcy_residual_fwd(const float* x0, const float* f_s, float inv_h0, float inv_h1,
                             float* residual, int B, int P, void* stream);

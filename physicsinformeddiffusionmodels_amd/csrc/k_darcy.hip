@@ -79,12 +79,9 @@ static bool darcy_stream_on() {
 static DarcyBands darcy_bands(int B, int P, bool res_only = false) {
   if (!res_only && darcy_full_on(B, P)) return DarcyBands{1, P};
   int nb = (1024 + B - 1) / B;              // >= 4 workgroups per CU where the batch alone does not provide them
-  static int max_rows = 0;                  // rows per band at large batches (PIDM_DARCY_ROWS, measurement knob; >= 4)
-  if (!max_rows) {
-    const char* e = knob("PIDM_DARCY_ROWS");
-    max_rows = e ? atoi(e) : 32;       // four-pixel kernel at batch 4096: 8 rows 343 us, 16 257, 24 275, 32 241, 64 265 (batch 1024: 60.7 / 61.9 / 54.8 / 61.1 for 16 / 24 / 32 / 64)
-    if (max_rows < 4) max_rows = 4;
-  }
+  const char* e = knob("PIDM_DARCY_ROWS");  // rows per band at large batches (measurement knob; >= 4)
+  int max_rows = e ? atoi(e) : 32;          // four-pixel kernel at batch 4096: 8 rows 343 us, 16 257, 24 275, 32 241, 64 265 (batch 1024: 60.7 / 61.9 / 54.8 / 61.1 for 16 / 24 / 32 / 64)
+  if (max_rows < 4) max_rows = 4;
   const int nb_min = (P + max_rows - 1) / max_rows;
   if (nb < nb_min) nb = nb_min;
   int nb_max = P / 4;
@@ -1183,6 +1180,11 @@ template <int MODE>
 static int launch_darcy(const float* x0, const float* pred, const float* f_s, const float* grad_res, const float* p2w,
                         const float* inv_var, const long long* tsteps, float c_data, float c_res, float inv_h0, float inv_h1,
                         float* residual, float* grad_pred, double* partial, int B, int P, hipStream_t st) {
+  // what the mode's kernels dereference (the loss weights are p2w / inv_var per sample, or the two schedule tables)
+  const bool have = MODE == DARCY_RES_ONLY ? (pred && f_s && residual)
+                  : MODE == DARCY_BWD      ? (pred && grad_res && grad_pred)
+                                           : (x0 && pred && f_s && p2w && inv_var && residual && grad_pred && partial);
+  if (!have) return fail("darcy: null buffer");
   if (B <= 0 || P < 5) return fail("darcy: need B>0 and P>=5 (got B=%d P=%d)", B, P);
   const DarcyBands bd = darcy_bands(B, P, MODE == DARCY_RES_ONLY);
   const int rows = darcy_lds_rows(P, bd.R);
@@ -1263,6 +1265,7 @@ static int launch_darcy(const float* x0, const float* pred, const float* f_s, co
 static int darcy_loss_impl(const float* x0, const float* x0_pred, const float* f_s, const float* p2w, const float* inv_var,
                            const long long* tsteps, float c_data, float c_residual, float inv_h0, float inv_h1, float* residual,
                            float* grad_x0_pred, float* out_scalars, void* workspace, int B, int P, hipStream_t st) {
+  if (!out_scalars) return fail("darcy: null buffer");
   double* partial = reinterpret_cast<double*>(workspace);
   int rc = launch_darcy<DARCY_LOSS>(x0, x0_pred, f_s, nullptr, p2w, inv_var, tsteps, c_data, c_residual, inv_h0, inv_h1, residual,
                                     grad_x0_pred, partial, B, P, st);
