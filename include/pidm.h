@@ -258,6 +258,26 @@ int pidm_mech_solve(const float* rho, const float* bcs, const float* kloc, int k
                     void* workspace, int B, void* stream);
 int pidm_floating_material(const float* rho, float threshold, int nel, int32_t* n_components, int B, void* stream);
 
+/* Posterior guidance of the mechanics sampler (csrc/k_guidance_mech.hip; no counterpart in the reference: an extension).
+ * With the quantities of pidm_mech_residual_fwd for an x0 estimate x0_pred [B,3,nel,nel] (nn = nel + 1): model_out [B,3,nn,nn] =
+ * (u bilinearly resized, rho zero padded), r = the row-replaced residual, shift = mean(rho) - vf; observations obs and a 0/1 mask
+ * (both [B,3,nn,nn]).  Per sample
+ *   L_obs = sum mask (model_out - obs)^2  (channel 2 over rows and columns < nel only: the zero padding is no part of the state,
+ *           whatever the mask says there),   L_pde = sum r^2,   L_vol = shift^2,
+ *   Phi = zeta_obs sqrt(L_obs) + zeta_pde sqrt(L_pde) + zeta_vol sqrt(L_vol)   (a term whose L is exactly 0 is omitted).
+ * ONE launch, one workgroup per sample on the LDS plan of the fused loss ((3 ndof + E) floats, so the same mesh limit): writes
+ * v [B,3,nel,nel] = dPhi/dx0_pred, model_out, and sums [B,3] = (L_obs, L_pde, L_vol) whatever the weights are; the sums are fp32
+ * roundings of fp64 fixed-tree sums (bit-identical run to run and across batch sizes). */
+int pidm_mech_guidance_cotangent(const float* x0_pred, const float* bcs, const float* vf, const float* obs, const float* mask,
+                                 float zeta_obs, float zeta_pde, float zeta_vol, const float* kloc, int kloc_stride,
+                                 const int32_t* elem_dofs, const int32_t* dof_elems, int nel, float* v, float* model_out, float* sums,
+                                 int B, void* stream);
+/* guided ancestral update on a state that the network sees resized: x_prev = c1 x0 + c2 x_t + sigma z - R^T g, everything
+ * [B,C,Ho,Ho] except g [B,Hi*Hi,Cg] (the UNet's input-gradient layout, channels 0..C-1 used).  R = pidm_bilinear_resize Ho -> Hi.
+ * Gather form, fixed order.  Any Hi, Ho >= 1; 1 <= C <= Cg <= 16; B <= 65535. */
+int pidm_psample_update_guided_resized(const float* x0, const float* x_t, const float* z, const float* g_nhwc, float c1, float c2,
+                                       float sigma, float* x_prev, int B, int C, int Cg, int Hi, int Ho, void* stream);
+
 /* Darcy training-data generation      replaces src/darcy_data_generation.py:118-163 (generate_sample: findiff assembly + dense lstsq)
  *   pidm_darcy_gen_acc: per sample b, K = exp(basis^T z_b) (basis [q, P*P] row-major, sqrt(eigenvalue)-scaled KLE modes; z [B, q],
  *                   1 <= q <= P^2) or, when z is NULL, K = K_in[b] ([B, P*P]); then p = the least-squares solution of the

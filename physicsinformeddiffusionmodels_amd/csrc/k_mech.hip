@@ -8,28 +8,9 @@
 // antialias=False == F.interpolate(align_corners=False)) and rho live in LDS (34 KB + 16 KB), HBM traffic is the
 // compulsory 48 KB in + ~85 KB out per sample.  Dirichlet rows (mask != 0) are identity rows with f -> 0, only rows
 // are replaced (K is not symmetrised), exactly as the reference does (:226-240).
-#include "pidm_launch.h"
+#include "k_mech_common.h"
 
 namespace pidm {
-
-struct MechMesh {
-  const int* elem_dofs;   // [E][8]
-  const int* dof_elems;   // [ndof][4][2] = (element, local index) or (-1, -1)
-  const float* kloc;      // [E][8][8] or [1][8][8] when kloc_stride == 0
-  int kloc_stride;        // 0 (uniform mesh) or 64
-  int E, ndof, nel, nn;   // nel = 64 elements per side, nn = 65 nodes per side
-};
-
-// source index / weight of torch's bilinear, align_corners=False, for output coordinate o
-__device__ __forceinline__ void bil_src(int o, int n_in, int n_out, int* i0, int* i1, float* lam) {
-  float src = ((float)o + 0.5f) * ((float)n_in / (float)n_out) - 0.5f;
-  if (src < 0.f) src = 0.f;
-  int a = (int)src;
-  if (a > n_in - 1) a = n_in - 1;
-  *i0 = a;
-  *i1 = (a < n_in - 1) ? a + 1 : a;
-  *lam = src - (float)a;
-}
 
 // generic square bilinear resize of [BC][Hi][Hi] -> [BC][Ho][Ho] (forward only: used on network INPUTS)
 __global__ void bilinear_resize_kernel(const float* __restrict__ in, float* __restrict__ out, int BC, int Hi, int Ho) {
@@ -630,12 +611,6 @@ extern "C" int pidm_bilinear_resize(const float* in, float* out, int BC, int Hi,
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(bilinear_resize_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), in, out, BC, Hi, Ho);
   PIDM_CHECK_LAUNCH("bilinear_resize_kernel");
-  return 0;
-}
-
-static int mech_args(int nel, int E, int ndof, const void* a, const void* b2, const void* c) {
-  if (!a || !b2 || !c) return fail("mech: null mesh table");
-  if (E != nel * nel || ndof != 2 * (nel + 1) * (nel + 1)) return fail("mech: mesh must be nel x nel quads with all dofs free");
   return 0;
 }
 

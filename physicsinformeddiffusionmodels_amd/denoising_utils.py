@@ -1052,6 +1052,123 @@ class DenoisingDiffusion(nn.Module):
             interm.append(x0p)
         return (x_seq, interm), {'residual': residual, 'guidance': guidance}
 
+    def p_sample_loop_guided_mechanics(self, conditioning_input, shape, residual_func, obs, mask, zeta_obs=1.0, zeta_pde=0.0,
+                                       zeta_vol=0.0, guide_below=None, surpress_noise=True, replace_observed=False,
+                                       keep_history=True):
+        """Conditional topology-optimisation sampling by posterior guidance (an extension: the reference has no counterpart).
+
+        conditioning_input: `(conditioning [B,3,nn,nn], bcs [B,4,nn,nn])`, or the 3-tuple `p_sample_loop` takes (the solution is
+        ignored); vf = conditioning[:,0,0,0] as in `p_sample`.  shape = (B,3,nn,nn), nn = nel + 1: the state is (u_x, u_y, rho
+        zero-padded) on the nodal grid.  obs, mask: [B,3,nn,nn] or broadcastable [1,3,nn,nn], mask 0/1: prescribed solid / void
+        regions or a partly known design (channel 2; its padding row and column are never observed, whatever the mask says), nodal
+        displacement readings (channels 0, 1).  At every step with t < `guide_below` (default: every step) x_t is moved against
+        the gradient, taken through the UNet and the nn -> nel resize of its input, of
+        Phi = zeta_obs sqrt(sum mask (model_out - obs)^2) + zeta_pde sqrt(sum r^2) + zeta_vol |mean(rho) - vf| of the model's x0
+        estimate: `input_gradient_pass` -> `ResidualsMechanics.guidance_cotangent` -> `pull` ->
+        x_{t-1} = c1 model_out + c2 x_t + sigma z - R^T d Phi / d net_in (four native calls besides the input resize; no weight
+        gradient is computed and no gradient state of the model is touched).  Steps at or above `guide_below` are the arithmetic of
+        `p_sample`.  `replace_observed=True` writes `obs` into the masked entries of the final state (not into the padding of
+        channel 2).
+
+        zeta_obs / zeta_pde / zeta_vol are user parameters.  Their defaults are PLACEHOLDERS: no trained checkpoint was available
+        when this was written, the right magnitudes depend on the model and the schedule, and nothing here claims sample quality.
+
+        Returns `((x_seq, interm), aux)`: aux['residual'] [B] = per-sample mean |r| of the final state (`pidm_mech_apply` with
+        rho = x[:,2,:-1,:-1]), aux['guidance'] [n_steps,B,3] = (L_obs, L_pde, L_vol) of the x0 estimate per step in the order the
+        steps are taken (zeros for unguided steps), kept on the device - nothing is read back inside the loop.
+
+        Not supported: compliance guidance, the `cond=` branch of the network, self-conditioning models, sample estimation
+        (`use_ddim_x0`) and meshes beyond the LDS limit of the mechanics kernels."""
+        from ._engine import frozen_weights, input_gradient_pass
+        from ._lib import PidmError
+        from .residuals_mechanics_K import ResidualsMechanics, _MechResidualFn, resize_image as resize_native
+        name = "p_sample_loop_guided_mechanics"
+        if not isinstance(residual_func, ResidualsMechanics):
+            raise PidmError(f"{name}: mechanics only (residual_func must be a ResidualsMechanics)")
+        if getattr(residual_func, 'use_ddim_x0', False):
+            raise PidmError(f"{name}: sample estimation (use_ddim_x0) is not supported")
+        net = residual_func.model
+        if getattr(net, 'self_condition', False):
+            raise PidmError(f"{name}: self-conditioning models are not supported")
+        nel = residual_func.pixels_per_dim
+        nn_ = nel + 1
+        shape = tuple(shape)
+        if len(shape) != 4 or shape[1:] != (3, nn_, nn_):
+            raise PidmError(f"{name}: shape must be (B,3,{nn_},{nn_}), got {shape}")
+        B = shape[0]
+        if not isinstance(conditioning_input, (tuple, list)) or len(conditioning_input) not in (2, 3):
+            raise PidmError(f"{name}: conditioning_input must be (conditioning, bcs) or (conditioning, bcs, solution)")
+        conditioning, bcs = conditioning_input[0], conditioning_input[1]
+        for nm, a, want in (('conditioning', conditioning, (B, 3, nn_, nn_)), ('bcs', bcs, (B, 4, nn_, nn_))):
+            if not torch.is_tensor(a) or tuple(a.shape) != want:
+                raise PidmError(f"{name}: {nm} must be {list(want)}, got {tuple(a.shape) if torch.is_tensor(a) else type(a).__name__}")
+        for nm, a in (('obs', obs), ('mask', mask)):
+            if not torch.is_tensor(a) or a.dim() != 4 or tuple(a.shape[1:]) != shape[1:] or a.shape[0] not in (1, B):
+                raise PidmError(f"{name}: {nm} must be [B,3,{nn_},{nn_}] or [1,3,{nn_},{nn_}] for shape {shape}, got "
+                                f"{tuple(a.shape) if torch.is_tensor(a) else type(a).__name__}")
+        dev = self.diff_dict['alphas'].device
+        lib, ht = self.lib, self._host_tables
+        obs_d = obs.detach().to(device=dev, dtype=torch.float32).expand(shape).contiguous()
+        mask_d = mask.detach().to(device=dev, dtype=torch.float32).expand(shape).contiguous()
+        cond_d = conditioning.detach().to(device=dev, dtype=torch.float32).contiguous()
+        bcs_d = bcs.detach().to(device=dev, dtype=torch.float32).contiguous()
+        vf = cond_d[:, 0, 0, 0].contiguous()
+        st = residual_func.stiffs
+        if st.kloc_dev.device != dev:
+            st.to(dev)
+        mesh = (ptr(st.kloc_dev), st.kloc_stride, ptr(st.elem_dofs32), ptr(st.dof_elems32), nel)
+        fixed_r = torch.cat((resize_native(cond_d, nel, lib), resize_native(bcs_d, nel, lib)), dim=1)     # resized once: 7 channels
+        guide_below = self.n_steps if guide_below is None else int(guide_below)
+        guidance = torch.zeros(self.n_steps, B, 3, dtype=torch.float32, device=dev)
+        cur_x = torch.randn(shape, device=dev)
+        x_seq = [cur_x.detach().cpu()] if keep_history else []
+        interm = [torch.zeros(shape)] if keep_history else []
+        with torch.no_grad(), frozen_weights(net):
+            for k, i in enumerate(reversed(range(self.n_steps))):
+                tt = torch.full((B,), i, device=dev, dtype=torch.long)
+                xi = cur_x.contiguous()
+                c1, c2 = float(ht['posterior_mean_coef1'][i]), float(ht['posterior_mean_coef2'][i])
+                sigma = 0.0 if (surpress_noise and i == 0) else float(ht['betas'][i].sqrt())
+                out = torch.empty_like(xi)
+                net_in = torch.cat((resize_native(xi, nel, lib), fixed_r), dim=1)                          # 10 channels
+                if i < guide_below:
+                    x0p, pull = input_gradient_pass(net, net_in, tt)
+                    v, mo, _ = residual_func.guidance_cotangent(x0p, bcs_d, vf, obs_d, mask_d, zeta_obs, zeta_pde, zeta_vol,
+                                                                sums_out=guidance[k])
+                    g = pull(v)
+                    z = torch.randn_like(xi)
+                    lib.check(lib.pidm_psample_update_guided_resized(ptr(mo), ptr(xi), ptr(z), ptr(g), c1, c2, sigma, ptr(out), B, 3,
+                                                                     g.shape[-1], nel, nn_, stream_ptr(dev)),
+                              'pidm_psample_update_guided_resized')
+                else:
+                    x0p = net(net_in, tt)
+                    _, mo, _, _ = _MechResidualFn.apply(x0p, bcs_d, vf, st, lib)
+                    z = torch.randn_like(xi)
+                    lib.check(lib.pidm_psample_update(ptr(mo), ptr(xi), ptr(z), c1, c2, sigma, ptr(out), xi.numel(),
+                                                      stream_ptr(dev)), 'pidm_psample_update')
+                cur_x = out
+                if keep_history:
+                    x_seq.append(cur_x.cpu())
+                    interm.append(mo.cpu())
+            if replace_observed:
+                on = mask_d != 0
+                on[:, 2, -1, :] = False
+                on[:, 2, :, -1] = False
+                cur_x = torch.where(on, obs_d, cur_x)
+                if keep_history:
+                    x_seq[-1] = cur_x.cpu()
+            rho = cur_x[:, 2, :-1, :-1].contiguous()
+            u_img = cur_x[:, :2].contiguous()
+            res = torch.empty(B, st.neq, dtype=torch.float32, device=dev)
+            comp = torch.empty(B, dtype=torch.float32, device=dev)
+            lib.check(lib.pidm_mech_apply(ptr(rho), ptr(u_img), ptr(bcs_d), *mesh, ptr(res), ptr(comp), B, stream_ptr(dev)),
+                      'pidm_mech_apply')
+            residual = res.abs().mean(dim=1)
+        if not keep_history:
+            x_seq.append(cur_x)
+            interm.append(mo)
+        return (x_seq, interm), {'residual': residual, 'guidance': guidance}
+
     def ddim_sample_x0(self, xt, t, model, shape, reduced_n_steps, ddim_sampling_eta, gov_eqs=None, self_cond=None):
         """Sample estimation (src/denoising_utils.py:712-788).  The reference walks ddim_steps + 2 time levels from t down to 0
         but never updates `model_input`: every model call sees the same x_t, the value it returns is

@@ -269,6 +269,46 @@ class ResidualsMechanics:
                 # cv2.connectedComponents counts the background label too: "!= 2" <=> not exactly one foreground component
                 'fm_error_full_batch': (ncomp != 1).to(torch.int64).cpu()}
 
+    def guidance_cotangent(self, x0_pred, bcs, vf, obs, mask, zeta_obs, zeta_pde, zeta_vol=0.0, sums_out=None):
+        """Posterior-guidance cotangent of an x0 estimate (csrc/k_guidance_mech.hip), one launch.  x0_pred [B,3,nel,nel] (u_x, u_y,
+        rho); bcs [B,4,nn,nn]; vf [B]; obs, mask [B,3,nn,nn] (mask 0/1) on the nodal grid nn = nel + 1 of model_out = (u resized,
+        rho zero-padded).  Per sample Phi = zeta_obs sqrt(L_obs) + zeta_pde sqrt(L_pde) + zeta_vol sqrt(L_vol) with
+        L_obs = sum mask (model_out - obs)^2 (the padding row and column of channel 2 are ignored whatever the mask says),
+        L_pde = sum r^2 of the residual K(rho) u - f and L_vol = (mean(rho) - vf)^2.  Returns `(v, model_out, sums)`:
+        v = dPhi/dx0_pred [B,3,nel,nel], model_out [B,3,nn,nn], sums [B,3] = (L_obs, L_pde, L_vol).  A term whose L is exactly 0
+        is omitted.  `sums_out`: a contiguous [B,3] fp32 tensor to write the sums into (no allocation, no copy).  Meshes whose
+        (3 ndof + E) floats do not fit one workgroup's LDS are refused, as by the residual adjoint.  No CPU fallback."""
+        nel = self.pixels_per_dim
+        nn = nel + 1
+        if not torch.is_tensor(x0_pred) or x0_pred.dim() != 4 or tuple(x0_pred.shape[1:]) != (3, nel, nel):
+            raise PidmError(f'guidance_cotangent: x0_pred must be [B,3,{nel},{nel}], got '
+                            f'{tuple(x0_pred.shape) if torch.is_tensor(x0_pred) else type(x0_pred).__name__}')
+        B = x0_pred.shape[0]
+        for name, a, want in (('bcs', bcs, (B, 4, nn, nn)), ('vf', vf, (B,)), ('obs', obs, (B, 3, nn, nn)), ('mask', mask, (B, 3, nn, nn))):
+            if not torch.is_tensor(a) or tuple(a.shape) != want:
+                raise PidmError(f'guidance_cotangent: {name} must be {list(want)}, got '
+                                f'{tuple(a.shape) if torch.is_tensor(a) else type(a).__name__}')
+        for name, a in (('x0_pred', x0_pred), ('bcs', bcs), ('vf', vf), ('obs', obs), ('mask', mask)):
+            if not a.dtype.is_floating_point:
+                raise PidmError(f'guidance_cotangent: {name} must be a floating-point tensor, got {a.dtype}')
+        if self._lib is None and not x0_pred.is_cuda:
+            raise PidmError('ResidualsMechanics needs tensors on an MI355X: the gfx950 kernels have no CPU fallback')
+        lib, dev, st = self.lib, x0_pred.device, self.stiffs
+        if st.kloc_dev.device != dev:
+            st.to(dev)
+        x = x0_pred.detach().contiguous().float()
+        bc, vfd, y, m = (a.detach().to(dev).contiguous().float() for a in (bcs, vf, obs, mask))
+        v = torch.empty_like(x)
+        mo = torch.empty(B, 3, nn, nn, dtype=torch.float32, device=dev)
+        sums = sums_out if sums_out is not None else torch.empty(B, 3, dtype=torch.float32, device=dev)
+        if tuple(sums.shape) != (B, 3) or sums.dtype != torch.float32 or not sums.is_contiguous() or sums.device != dev:
+            raise PidmError('guidance_cotangent: sums_out must be a contiguous fp32 [B,3] tensor on the input device')
+        lib.check(lib.pidm_mech_guidance_cotangent(ptr(x), ptr(bc), ptr(vfd), ptr(y), ptr(m), float(zeta_obs), float(zeta_pde),
+                                                   float(zeta_vol), ptr(st.kloc_dev), st.kloc_stride, ptr(st.elem_dofs32),
+                                                   ptr(st.dof_elems32), nel, ptr(v), ptr(mo), ptr(sums), B, stream_ptr(dev)),
+                  'pidm_mech_guidance_cotangent')
+        return v, mo, sums
+
     def compute_residual(self, input_tuple, reduce='none', return_model_out=False, return_optimizer=False,
                          return_inequality=False, sample=False, ddim_func=None, pass_through=False):
         self.deriv_mode = 'stiffness'
