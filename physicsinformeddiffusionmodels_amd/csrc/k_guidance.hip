@@ -11,200 +11,158 @@
 // x and the store of v lives in LDS.  The adjoint is LINEAR in r, so the six transposed-stencil operands are built from the
 // unscaled residual in the same pass that sums r^2, and 1 / sqrt(L_pde) multiplies the gathered result: the residual is never
 // written out and never re-read.  LDS plan (floats, F = P*P): p | K | -K r | a0 | a1 | b0 | b1 | d  = 8 F (128 KiB at P = 64) +
-// 2 x 4 doubles of the block sums.  Same taps, same order as darcy_kernel (k_darcy.hip): its adjoint figures carry over.
-// The two sums are fp64: a thread adds its pixels in index order, then a fixed shuffle tree and four wave sums - no atomics, the
-// same bits run to run and for any batch size (a sample never sees another one).
+// 2 x 4 doubles of the block sums.  The taps are darcy_kernel's own (k_darcy_stencil.h, window 0 .. P-1), taken in its order: its
+// adjoint figures carry over.
+// The sums are fp64: a thread adds its pixels in index order, then block_sum_f64 (pidm_common.h) - no atomics, the same bits run
+// to run and for any batch size (a sample never sees another one).
+#include "k_darcy_stencil.h"
 #include "pidm_common.h"
 
 namespace pidm {
 
-struct GdAxis {          // acc-2 coefficients / h^order: class 0 low edge, 1 centre, 2 high edge (as FdAxis of k_darcy.hip)
-  float c1[3][4];
-  float c2[3][4];
+// ---- pieces shared by the two LDS-resident kernels (guidance_cotangent_kernel, guidance_cotangent_flux_kernel) -----------------
+struct GdFields {      // the 8 F floats of dynamic LDS
+  float* p;
+  float* K;
+  float* kg;           // -K r_eq
+  float* a0;           // coefficient on p0 (flux kernel: residual and flux parts)
+  float* a1;           // coefficient on p1
+  float* b0;           // coefficient on K0
+  float* b1;           // coefficient on K1
+  float* d;            // direct dependence of eq (and of the flux) on K at the same pixel
 };
-static GdAxis gd_axis(double inv_h) {
-  static const double c1[3][3] = {{-1.5, 2.0, -0.5}, {-0.5, 0.0, 0.5}, {1.5, -2.0, 0.5}};
-  static const double c2[3][4] = {{2.0, -5.0, 4.0, -1.0}, {1.0, -2.0, 1.0, 0.0}, {2.0, -5.0, 4.0, -1.0}};
-  GdAxis a;
-  for (int c = 0; c < 3; ++c)
-    for (int k = 0; k < 4; ++k) {
-      a.c1[c][k] = (k < 3) ? (float)(c1[c][k] * inv_h) : 0.f;
-      a.c2[c][k] = (float)(c2[c][k] * inv_h * inv_h);
-    }
-  return a;
+__device__ __forceinline__ GdFields gd_fields(float* smem, int F) {
+  return GdFields{smem, smem + F, smem + 2 * F, smem + 3 * F, smem + 4 * F, smem + 5 * F, smem + 6 * F, smem + 7 * F};
 }
-// forward taps of line position i: 4 (index, weight) pairs; zero-weight taps keep an index inside [0, P)
-struct GdTaps4 {
-  int idx[4];
-  float w1[4], w2[4];
+// pixel (i, j) of n = tid, tid + 256, ... without a division per pixel
+struct GdWalk {
+  int i, j, di, dj;
+  __device__ __forceinline__ GdWalk(int tid, int P) : i(tid / P), j(tid - (tid / P) * P), di(256 / P), dj(256 % P) {}
+  __device__ __forceinline__ void step(int P) {
+    j += dj;
+    i += di;
+    if (j >= P) {
+      j -= P;
+      ++i;
+    }
+  }
 };
-__device__ __forceinline__ GdTaps4 gd_taps(const GdAxis& ax, int i, int P) {
-  GdTaps4 t;
-  const bool low = i == 0, high = i == P - 1;
+// x -> LDS (p | K); returns this thread's part of L_obs.  The caller's barrier publishes the two fields.
+__device__ __forceinline__ double gd_stage(const float* __restrict__ xb, const float* __restrict__ yb, const float* __restrict__ mb,
+                                           const GdFields& s, int N, int tid) {
+  double acc_obs = 0.0;
+  for (int n = tid; n < N; n += 256) {
+    const float vp = xb[n], vK = xb[N + n];
+    s.p[n] = vp;
+    s.K[n] = vK;
+    const float d0 = vp - yb[n], d1 = vK - yb[N + n];
+    acc_obs += (double)(mb[n] * (d0 * d0)) + (double)(mb[N + n] * (d1 * d1));
+  }
+  return acc_obs;
+}
+// the forward stencil walk: the six derivatives at pixel (i, j)
+struct GdDerivs {
+  float p0, p00, K0, p1, p11, K1;
+};
+__device__ __forceinline__ GdDerivs gd_derivs(const float* sp, const float* sK, const FdAxis& ax0, const FdAxis& ax1, int i, int j,
+                                              int P) {
+  const FdTaps4 ti = fd_taps(ax0, i, P, 0, P - 1), tj = fd_taps(ax1, j, P, 0, P - 1);
+  GdDerivs d = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    int ix = high ? P - 1 - k : (low ? k : i - 1 + k);
-    ix = ix < 0 ? 0 : (ix > P - 1 ? P - 1 : ix);
-    t.idx[k] = ix;
-    const float c1i = (k < 3) ? ax.c1[1][k] : 0.f, c2i = (k < 3) ? ax.c2[1][k] : 0.f;
-    t.w1[k] = high ? ax.c1[2][k] : (low ? ax.c1[0][k] : c1i);
-    t.w2[k] = high ? ax.c2[2][k] : (low ? ax.c2[0][k] : c2i);
+    const float pa = sp[ti.idx[k] * P + j], pr = sp[i * P + tj.idx[k]];
+    d.p0 = fmaf(ti.w1[k], pa, d.p0);
+    d.p00 = fmaf(ti.w2[k], pa, d.p00);
+    d.p1 = fmaf(tj.w1[k], pr, d.p1);
+    d.p11 = fmaf(tj.w2[k], pr, d.p11);
+    if (k < 3) {
+      d.K0 = fmaf(ti.w1[k], sK[ti.idx[k] * P + j], d.K0);
+      d.K1 = fmaf(tj.w1[k], sK[i * P + tj.idx[k]], d.K1);
+    }
   }
-  return t;
+  return d;
 }
-// transposed taps of column m: rows 0, P-1, m-1, m, m+1 (rows that do not touch m get weight 0 and a clamped index)
-struct GdTaps5 {
-  int idx[5];
-  float w1[5], w2[5];
+// the residual terms from the derivatives: eq BEFORE f_s is subtracted, the boundary signs and the two boundary channels
+struct GdResid {
+  float eq, s0, s1, bc0, bc1;
 };
-__device__ __forceinline__ GdTaps5 gd_taps_T(const GdAxis& ax, int m, int P) {
-  GdTaps5 t;
-  const int rows[5] = {0, P - 1, m - 1, m, m + 1};
+__device__ __forceinline__ GdResid gd_resid(const GdDerivs& d, float Kv, float bc1_sign, int i, int j, int P) {
+  GdResid r;
+  const float vj00 = -Kv * d.p00 - d.K0 * d.p0;
+  const float vj11 = -Kv * d.p11 - d.K1 * d.p1;
+  r.eq = vj00 + vj11;
+  r.s0 = (i == 0) ? -1.f : ((i == P - 1) ? 1.f : 0.f);
+  r.s1 = (j == 0) ? bc1_sign : ((j == P - 1) ? -bc1_sign : 0.f);
+  r.bc0 = r.s0 * d.p0;
+  r.bc1 = r.s1 * d.p1;
+  return r;
+}
+// the transposed gather at pixel n = (i, j) from the six operand fields: (J^T .) on the p and on the K channel
+struct GdGrad {
+  float gp, gK;
+};
+__device__ __forceinline__ GdGrad gd_gather(const GdFields& s, const FdAxis& ax0, const FdAxis& ax1, int i, int j, int n, int P) {
+  const FdTaps5 ti = fd_taps_T(ax0, i, P, 0, P - 1), tj = fd_taps_T(ax1, j, P, 0, P - 1);
+  float g00 = 0.f, g11 = 0.f, ga0 = 0.f, ga1 = 0.f, gb0 = 0.f, gb1 = 0.f;
 #pragma unroll
   for (int k = 0; k < 5; ++k) {
-    const int i = rows[k];
-    float a1 = 0.f, a2 = 0.f;
-    if (k == 0) {
-      const int q = m < 4 ? m : 3;
-      a1 = (m < 3) ? ax.c1[0][q] : 0.f;
-      a2 = (m < 4) ? ax.c2[0][q] : 0.f;
-    } else if (k == 1) {
-      const int d = P - 1 - m, q = d < 4 ? d : 3;
-      a1 = (d < 3) ? ax.c1[2][q] : 0.f;
-      a2 = (d < 4) ? ax.c2[2][q] : 0.f;
-    } else {
-      const bool ok = (i >= 1) & (i <= P - 2);
-      const int q = m - (i - 1);          // 2, 1, 0 for k = 2, 3, 4
-      a1 = ok ? ax.c1[1][q] : 0.f;
-      a2 = ok ? ax.c2[1][q] : 0.f;
-    }
-    t.w1[k] = a1;
-    t.w2[k] = a2;
-    t.idx[k] = i < 0 ? 0 : (i > P - 1 ? P - 1 : i);
+    const int c0 = ti.idx[k] * P + j, c1 = i * P + tj.idx[k];
+    g00 = fmaf(ti.w2[k], s.kg[c0], g00);
+    ga0 = fmaf(ti.w1[k], s.a0[c0], ga0);
+    gb0 = fmaf(ti.w1[k], s.b0[c0], gb0);
+    g11 = fmaf(tj.w2[k], s.kg[c1], g11);
+    ga1 = fmaf(tj.w1[k], s.a1[c1], ga1);
+    gb1 = fmaf(tj.w1[k], s.b1[c1], gb1);
   }
-  return t;
+  return GdGrad{((g00 + g11) + ga0) + ga1, (s.d[n] + gb0) + gb1};
 }
-
-// fixed-order block sum of two doubles (256 threads = 4 waves); every thread returns with both totals
-__device__ __forceinline__ void gd_block_sum2(double& a, double& b, double (*red)[4], int tid) {
-  for (int off = 32; off > 0; off >>= 1) {
-    a += __shfl_down(a, off);
-    b += __shfl_down(b, off);
-  }
-  if ((tid & 63) == 0) {
-    red[0][tid >> 6] = a;
-    red[1][tid >> 6] = b;
-  }
-  __syncthreads();
-  a = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
-  b = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
-}
-// zeta / sqrt(L), rounded once to fp32; exactly 0 when the term is absent
-__device__ __forceinline__ float gd_scale(float zeta, double L) { return (L > 0.0 && zeta != 0.f) ? (float)((double)zeta / sqrt(L)) : 0.f; }
 
 __global__ void __launch_bounds__(256) guidance_cotangent_kernel(const float* __restrict__ xh, const float* __restrict__ y,
                                                                  const float* __restrict__ msk,
                                                                  const float* __restrict__ f_s, float zeta_obs, float zeta_pde,
-                                                                 float bc1_sign, GdAxis ax0, GdAxis ax1, float* __restrict__ v,
+                                                                 float bc1_sign, FdAxis ax0, FdAxis ax1, float* __restrict__ v,
                                                                  float* __restrict__ sums, int P) {
   HIP_DYNAMIC_SHARED(float, smem)
   __shared__ double red[2][4];
-  const int N = P * P, F = N;
+  const int N = P * P;
   const int b = blockIdx.x, tid = threadIdx.x;
-  float* sp = smem;
-  float* sK = sp + F;
-  float* skg = sp + 2 * F;    // -K r_eq
-  float* sa0 = sp + 3 * F;    // coefficient on p0
-  float* sa1 = sp + 4 * F;    // coefficient on p1
-  float* sb0 = sp + 5 * F;    // coefficient on K0
-  float* sb1 = sp + 6 * F;    // coefficient on K1
-  float* sd = sp + 7 * F;     // direct dependence of eq on K at the same pixel
+  const GdFields s = gd_fields(smem, N);
   const float* xb = xh + (size_t)b * 2 * N;
   const float* yb = y + (size_t)b * 2 * N;
   const float* mb = msk + (size_t)b * 2 * N;
-  const int dj = 256 % P, di = 256 / P;
 
-  double acc_obs = 0.0, acc_r2 = 0.0;
-  for (int n = tid; n < N; n += 256) {
-    const float vp = xb[n], vK = xb[N + n];
-    sp[n] = vp;
-    sK[n] = vK;
-    const float d0 = vp - yb[n], d1 = vK - yb[N + n];
-    acc_obs += (double)(mb[n] * (d0 * d0)) + (double)(mb[N + n] * (d1 * d1));
-  }
+  double L[2] = {gd_stage(xb, yb, mb, s, N, tid), 0.0};     // L_obs, L_pde
   __syncthreads();
   {
-    int i = tid / P, j = tid - (tid / P) * P;
-    for (int n = tid; n < N; n += 256) {
-      const GdTaps4 ti = gd_taps(ax0, i, P), tj = gd_taps(ax1, j, P);
-      float p0 = 0.f, p00 = 0.f, K0 = 0.f, p1 = 0.f, p11 = 0.f, K1 = 0.f;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float pa = sp[ti.idx[k] * P + j], pr = sp[i * P + tj.idx[k]];
-        p0 = fmaf(ti.w1[k], pa, p0);
-        p00 = fmaf(ti.w2[k], pa, p00);
-        p1 = fmaf(tj.w1[k], pr, p1);
-        p11 = fmaf(tj.w2[k], pr, p11);
-        if (k < 3) {
-          K0 = fmaf(ti.w1[k], sK[ti.idx[k] * P + j], K0);
-          K1 = fmaf(tj.w1[k], sK[i * P + tj.idx[k]], K1);
-        }
-      }
-      const float Kv = sK[n];
-      const float vj00 = -Kv * p00 - K0 * p0;
-      const float vj11 = -Kv * p11 - K1 * p1;
-      const float eq = vj00 + vj11 - f_s[n];
-      const float s0 = (i == 0) ? -1.f : ((i == P - 1) ? 1.f : 0.f);
-      const float s1 = (j == 0) ? bc1_sign : ((j == P - 1) ? -bc1_sign : 0.f);
-      const float bc0 = s0 * p0, bc1 = s1 * p1;
-      acc_r2 += (double)(eq * eq) + (double)(bc0 * bc0) + (double)(bc1 * bc1);
-      skg[n] = -Kv * eq;
-      sa0[n] = -K0 * eq + s0 * bc0;
-      sa1[n] = -K1 * eq + s1 * bc1;
-      sb0[n] = -p0 * eq;
-      sb1[n] = -p1 * eq;
-      sd[n] = -(p00 + p11) * eq;
-      j += dj;
-      i += di;
-      if (j >= P) {
-        j -= P;
-        ++i;
-      }
+    GdWalk q(tid, P);
+    for (int n = tid; n < N; n += 256, q.step(P)) {
+      const GdDerivs d = gd_derivs(s.p, s.K, ax0, ax1, q.i, q.j, P);
+      const float Kv = s.K[n];
+      const GdResid r = gd_resid(d, Kv, bc1_sign, q.i, q.j, P);
+      const float eq = r.eq - f_s[n];
+      L[1] += (double)(eq * eq) + (double)(r.bc0 * r.bc0) + (double)(r.bc1 * r.bc1);
+      s.kg[n] = -Kv * eq;
+      s.a0[n] = -d.K0 * eq + r.s0 * r.bc0;
+      s.a1[n] = -d.K1 * eq + r.s1 * r.bc1;
+      s.b0[n] = -d.p0 * eq;
+      s.b1[n] = -d.p1 * eq;
+      s.d[n] = -(d.p00 + d.p11) * eq;
     }
   }
-  gd_block_sum2(acc_obs, acc_r2, red, tid);     // (its barrier also publishes the six operand fields)
-  const float so = gd_scale(zeta_obs, acc_obs), sr = gd_scale(zeta_pde, acc_r2);
+  block_sum_f64<2>(L, red, tid);     // (its barrier also publishes the six operand fields)
+  const float so = guidance_scale(zeta_obs, L[0]), sr = guidance_scale(zeta_pde, L[1]);
   if (tid == 0) {
-    sums[2 * b] = (float)acc_obs;
-    sums[2 * b + 1] = (float)acc_r2;
+    sums[2 * b] = (float)L[0];
+    sums[2 * b + 1] = (float)L[1];
   }
   {
-    int i = tid / P, j = tid - (tid / P) * P;
+    GdWalk q(tid, P);
     float* vb = v + (size_t)b * 2 * N;
-    for (int n = tid; n < N; n += 256) {
-      const GdTaps5 ti = gd_taps_T(ax0, i, P), tj = gd_taps_T(ax1, j, P);
-      float g00 = 0.f, g11 = 0.f, ga0 = 0.f, ga1 = 0.f, gb0 = 0.f, gb1 = 0.f;
-#pragma unroll
-      for (int k = 0; k < 5; ++k) {
-        const int c0 = ti.idx[k] * P + j, c1 = i * P + tj.idx[k];
-        g00 = fmaf(ti.w2[k], skg[c0], g00);
-        ga0 = fmaf(ti.w1[k], sa0[c0], ga0);
-        gb0 = fmaf(ti.w1[k], sb0[c0], gb0);
-        g11 = fmaf(tj.w2[k], skg[c1], g11);
-        ga1 = fmaf(tj.w1[k], sa1[c1], ga1);
-        gb1 = fmaf(tj.w1[k], sb1[c1], gb1);
-      }
-      const float gp = ((g00 + g11) + ga0) + ga1;
-      const float gK = (sd[n] + gb0) + gb1;
-      const float op = so * (mb[n] * (sp[n] - yb[n])), oK = so * (mb[N + n] * (sK[n] - yb[N + n]));
-      vb[n] = fmaf(sr, gp, op);
-      vb[N + n] = fmaf(sr, gK, oK);
-      j += dj;
-      i += di;
-      if (j >= P) {
-        j -= P;
-        ++i;
-      }
+    for (int n = tid; n < N; n += 256, q.step(P)) {
+      const GdGrad g = gd_gather(s, ax0, ax1, q.i, q.j, n, P);
+      const float op = so * (mb[n] * (s.p[n] - yb[n])), oK = so * (mb[N + n] * (s.K[n] - yb[N + n]));
+      vb[n] = fmaf(sr, g.gp, op);
+      vb[N + n] = fmaf(sr, g.gK, oK);
     }
   }
 }
@@ -222,18 +180,18 @@ __global__ void __launch_bounds__(256) guidance_scale_general_kernel(const float
   const float* yb = y + (size_t)b * 2 * N;
   const float* mb = msk + (size_t)b * 2 * N;
   const float* rb = res + (size_t)b * 3 * N;
-  double acc_obs = 0.0, acc_r2 = 0.0;
+  double L[2] = {0.0, 0.0};     // L_obs, L_pde
   for (int n = tid; n < N; n += 256) {
     const float d0 = xb[n] - yb[n], d1 = xb[N + n] - yb[N + n];
-    acc_obs += (double)(mb[n] * (d0 * d0)) + (double)(mb[N + n] * (d1 * d1));
+    L[0] += (double)(mb[n] * (d0 * d0)) + (double)(mb[N + n] * (d1 * d1));
     const float r0 = rb[3 * n], r1 = rb[3 * n + 1], r2 = rb[3 * n + 2];
-    acc_r2 += (double)(r0 * r0) + (double)(r1 * r1) + (double)(r2 * r2);
+    L[1] += (double)(r0 * r0) + (double)(r1 * r1) + (double)(r2 * r2);
   }
-  gd_block_sum2(acc_obs, acc_r2, red, tid);
-  const float so = gd_scale(zeta_obs, acc_obs), sr = gd_scale(zeta_pde, acc_r2);
+  block_sum_f64<2>(L, red, tid);
+  const float so = guidance_scale(zeta_obs, L[0]), sr = guidance_scale(zeta_pde, L[1]);
   if (tid == 0) {
-    sums[2 * b] = (float)acc_obs;
-    sums[2 * b + 1] = (float)acc_r2;
+    sums[2 * b] = (float)L[0];
+    sums[2 * b + 1] = (float)L[1];
   }
   for (int n = tid; n < 2 * N; n += 256) v_obs[(size_t)b * 2 * N + n] = so * (mb[n] * (xb[n] - yb[n]));
   for (int n = tid; n < 3 * N; n += 256) gres[(size_t)b * 3 * N + n] = sr * rb[n];
@@ -249,161 +207,70 @@ __global__ void __launch_bounds__(256) guidance_scale_general_kernel(const float
 // pass 1 walks the stencils from the LDS-resident p and K and only sums; pass 2 walks them again (same taps, same order, so the
 // same bits) and stores s_r (...) + s_f (-K e_c) into a0 / a1 and s_r (...) + s_f (-sum e_c p_c) into d; the gather is unchanged.
 // y_q and m_q are read from global in both passes (the second read comes out of L2).
-struct GdDerivs {
-  float p0, p00, K0, p1, p11, K1;
-};
-__device__ __forceinline__ GdDerivs gd_derivs(const float* sp, const float* sK, const GdAxis& ax0, const GdAxis& ax1, int i, int j,
-                                              int P) {
-  const GdTaps4 ti = gd_taps(ax0, i, P), tj = gd_taps(ax1, j, P);
-  GdDerivs d = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const float pa = sp[ti.idx[k] * P + j], pr = sp[i * P + tj.idx[k]];
-    d.p0 = fmaf(ti.w1[k], pa, d.p0);
-    d.p00 = fmaf(ti.w2[k], pa, d.p00);
-    d.p1 = fmaf(tj.w1[k], pr, d.p1);
-    d.p11 = fmaf(tj.w2[k], pr, d.p11);
-    if (k < 3) {
-      d.K0 = fmaf(ti.w1[k], sK[ti.idx[k] * P + j], d.K0);
-      d.K1 = fmaf(tj.w1[k], sK[i * P + tj.idx[k]], d.K1);
-    }
-  }
-  return d;
-}
-__device__ __forceinline__ void gd_block_sum3(double& a, double& b, double& c, double (*red)[4], int tid) {
-  for (int off = 32; off > 0; off >>= 1) {
-    a += __shfl_down(a, off);
-    b += __shfl_down(b, off);
-    c += __shfl_down(c, off);
-  }
-  if ((tid & 63) == 0) {
-    red[0][tid >> 6] = a;
-    red[1][tid >> 6] = b;
-    red[2][tid >> 6] = c;
-  }
-  __syncthreads();
-  a = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
-  b = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
-  c = ((red[2][0] + red[2][1]) + red[2][2]) + red[2][3];
-}
-
 __global__ void __launch_bounds__(256) guidance_cotangent_flux_kernel(const float* __restrict__ xh, const float* __restrict__ y,
                                                                       const float* __restrict__ msk, const float* __restrict__ yq,
                                                                       const float* __restrict__ mq, const float* __restrict__ f_s,
                                                                       float zeta_obs, float zeta_pde, float zeta_flux, float bc1_sign,
-                                                                      GdAxis ax0, GdAxis ax1, float* __restrict__ v,
+                                                                      FdAxis ax0, FdAxis ax1, float* __restrict__ v,
                                                                       float* __restrict__ sums, int P) {
   HIP_DYNAMIC_SHARED(float, smem)
   __shared__ double red[3][4];
-  const int N = P * P, F = N;
+  const int N = P * P;
   const int b = blockIdx.x, tid = threadIdx.x;
-  float* sp = smem;
-  float* sK = sp + F;
-  float* skg = sp + 2 * F;    // s_r (-K r_eq)
-  float* sa0 = sp + 3 * F;    // coefficient on p0 (residual and flux parts)
-  float* sa1 = sp + 4 * F;    // coefficient on p1
-  float* sb0 = sp + 5 * F;    // coefficient on K0
-  float* sb1 = sp + 6 * F;    // coefficient on K1
-  float* sd = sp + 7 * F;     // direct dependence on K at the same pixel
+  const GdFields s = gd_fields(smem, N);
   const float* xb = xh + (size_t)b * 2 * N;
   const float* yb = y + (size_t)b * 2 * N;
   const float* mb = msk + (size_t)b * 2 * N;
   const float* yqb = yq + (size_t)b * 2 * N;
   const float* mqb = mq + (size_t)b * 2 * N;
-  const int dj = 256 % P, di = 256 / P;
 
-  double acc_obs = 0.0, acc_r2 = 0.0, acc_fl = 0.0;
-  for (int n = tid; n < N; n += 256) {
-    const float vp = xb[n], vK = xb[N + n];
-    sp[n] = vp;
-    sK[n] = vK;
-    const float d0 = vp - yb[n], d1 = vK - yb[N + n];
-    acc_obs += (double)(mb[n] * (d0 * d0)) + (double)(mb[N + n] * (d1 * d1));
-  }
+  double L[3] = {gd_stage(xb, yb, mb, s, N, tid), 0.0, 0.0};     // L_obs, L_pde, L_flux
   __syncthreads();
   {
-    int i = tid / P, j = tid - (tid / P) * P;
-    for (int n = tid; n < N; n += 256) {
-      const GdDerivs d = gd_derivs(sp, sK, ax0, ax1, i, j, P);
-      const float Kv = sK[n];
-      const float vj00 = -Kv * d.p00 - d.K0 * d.p0;
-      const float vj11 = -Kv * d.p11 - d.K1 * d.p1;
-      const float eq = vj00 + vj11 - f_s[n];
-      const float s0 = (i == 0) ? -1.f : ((i == P - 1) ? 1.f : 0.f);
-      const float s1 = (j == 0) ? bc1_sign : ((j == P - 1) ? -bc1_sign : 0.f);
-      const float bc0 = s0 * d.p0, bc1 = s1 * d.p1;
-      acc_r2 += (double)(eq * eq) + (double)(bc0 * bc0) + (double)(bc1 * bc1);
+    GdWalk q(tid, P);
+    for (int n = tid; n < N; n += 256, q.step(P)) {
+      const GdDerivs d = gd_derivs(s.p, s.K, ax0, ax1, q.i, q.j, P);
+      const float Kv = s.K[n];
+      const GdResid r = gd_resid(d, Kv, bc1_sign, q.i, q.j, P);
+      const float eq = r.eq - f_s[n];
+      L[1] += (double)(eq * eq) + (double)(r.bc0 * r.bc0) + (double)(r.bc1 * r.bc1);
       const float f0 = -Kv * d.p0 - yqb[n], f1 = -Kv * d.p1 - yqb[N + n];
-      acc_fl += (double)(mqb[n] * (f0 * f0)) + (double)(mqb[N + n] * (f1 * f1));
-      j += dj;
-      i += di;
-      if (j >= P) {
-        j -= P;
-        ++i;
-      }
+      L[2] += (double)(mqb[n] * (f0 * f0)) + (double)(mqb[N + n] * (f1 * f1));
     }
   }
-  gd_block_sum3(acc_obs, acc_r2, acc_fl, red, tid);
-  const float so = gd_scale(zeta_obs, acc_obs), sr = gd_scale(zeta_pde, acc_r2), sf = gd_scale(zeta_flux, acc_fl);
+  block_sum_f64<3>(L, red, tid);
+  const float so = guidance_scale(zeta_obs, L[0]), sr = guidance_scale(zeta_pde, L[1]), sf = guidance_scale(zeta_flux, L[2]);
   if (tid == 0) {
-    sums[3 * b] = (float)acc_obs;
-    sums[3 * b + 1] = (float)acc_r2;
-    sums[3 * b + 2] = (float)acc_fl;
+    sums[3 * b] = (float)L[0];
+    sums[3 * b + 1] = (float)L[1];
+    sums[3 * b + 2] = (float)L[2];
   }
   {
-    int i = tid / P, j = tid - (tid / P) * P;
-    for (int n = tid; n < N; n += 256) {
-      const GdDerivs d = gd_derivs(sp, sK, ax0, ax1, i, j, P);
-      const float Kv = sK[n];
-      const float vj00 = -Kv * d.p00 - d.K0 * d.p0;
-      const float vj11 = -Kv * d.p11 - d.K1 * d.p1;
-      const float eq = sr * (vj00 + vj11 - f_s[n]);
-      const float s0 = (i == 0) ? -1.f : ((i == P - 1) ? 1.f : 0.f);
-      const float s1 = (j == 0) ? bc1_sign : ((j == P - 1) ? -bc1_sign : 0.f);
-      const float bc0 = sr * (s0 * d.p0), bc1 = sr * (s1 * d.p1);
+    GdWalk q(tid, P);
+    for (int n = tid; n < N; n += 256, q.step(P)) {
+      const GdDerivs d = gd_derivs(s.p, s.K, ax0, ax1, q.i, q.j, P);
+      const float Kv = s.K[n];
+      const GdResid r = gd_resid(d, Kv, bc1_sign, q.i, q.j, P);
+      const float eq = sr * (r.eq - f_s[n]);
+      const float bc0 = sr * r.bc0, bc1 = sr * r.bc1;
       const float e0 = sf * (mqb[n] * (-Kv * d.p0 - yqb[n])), e1 = sf * (mqb[N + n] * (-Kv * d.p1 - yqb[N + n]));
-      skg[n] = -Kv * eq;
-      sa0[n] = (-d.K0 * eq + s0 * bc0) - Kv * e0;
-      sa1[n] = (-d.K1 * eq + s1 * bc1) - Kv * e1;
-      sb0[n] = -d.p0 * eq;
-      sb1[n] = -d.p1 * eq;
-      sd[n] = -(d.p00 + d.p11) * eq - (e0 * d.p0 + e1 * d.p1);
-      j += dj;
-      i += di;
-      if (j >= P) {
-        j -= P;
-        ++i;
-      }
+      s.kg[n] = -Kv * eq;
+      s.a0[n] = (-d.K0 * eq + r.s0 * bc0) - Kv * e0;
+      s.a1[n] = (-d.K1 * eq + r.s1 * bc1) - Kv * e1;
+      s.b0[n] = -d.p0 * eq;
+      s.b1[n] = -d.p1 * eq;
+      s.d[n] = -(d.p00 + d.p11) * eq - (e0 * d.p0 + e1 * d.p1);
     }
   }
   __syncthreads();
   {
-    int i = tid / P, j = tid - (tid / P) * P;
+    GdWalk q(tid, P);
     float* vb = v + (size_t)b * 2 * N;
-    for (int n = tid; n < N; n += 256) {
-      const GdTaps5 ti = gd_taps_T(ax0, i, P), tj = gd_taps_T(ax1, j, P);
-      float g00 = 0.f, g11 = 0.f, ga0 = 0.f, ga1 = 0.f, gb0 = 0.f, gb1 = 0.f;
-#pragma unroll
-      for (int k = 0; k < 5; ++k) {
-        const int c0 = ti.idx[k] * P + j, c1 = i * P + tj.idx[k];
-        g00 = fmaf(ti.w2[k], skg[c0], g00);
-        ga0 = fmaf(ti.w1[k], sa0[c0], ga0);
-        gb0 = fmaf(ti.w1[k], sb0[c0], gb0);
-        g11 = fmaf(tj.w2[k], skg[c1], g11);
-        ga1 = fmaf(tj.w1[k], sa1[c1], ga1);
-        gb1 = fmaf(tj.w1[k], sb1[c1], gb1);
-      }
-      const float gp = ((g00 + g11) + ga0) + ga1;
-      const float gK = (sd[n] + gb0) + gb1;
-      const float op = so * (mb[n] * (sp[n] - yb[n])), oK = so * (mb[N + n] * (sK[n] - yb[N + n]));
-      vb[n] = gp + op;
-      vb[N + n] = gK + oK;
-      j += dj;
-      i += di;
-      if (j >= P) {
-        j -= P;
-        ++i;
-      }
+    for (int n = tid; n < N; n += 256, q.step(P)) {
+      const GdGrad g = gd_gather(s, ax0, ax1, q.i, q.j, n, P);
+      const float op = so * (mb[n] * (s.p[n] - yb[n])), oK = so * (mb[N + n] * (s.K[n] - yb[N + n]));
+      vb[n] = g.gp + op;
+      vb[N + n] = g.gK + oK;
     }
   }
 }
@@ -418,27 +285,27 @@ __global__ void __launch_bounds__(256) guidance_flux_general_kernel(const float*
                                                                     const float* __restrict__ mq, float zeta_flux,
                                                                     const float* __restrict__ sums2, float* __restrict__ sums3,
                                                                     float* __restrict__ w, const float* v_in, float* v_out, int N) {
-  __shared__ double red[3][4];
+  __shared__ double red[1][4];
   const int b = blockIdx.x, tid = threadIdx.x;
   const float* Kb = xh + (size_t)b * 2 * N + N;
   const float* d0b = dp0 + (size_t)b * N;
   const float* d1b = dp1 + (size_t)b * N;
   const float* yqb = yq + (size_t)b * 2 * N;
   const float* mqb = mq + (size_t)b * 2 * N;
-  double acc_fl = 0.0, z0 = 0.0, z1 = 0.0;
+  double L[1] = {0.0};     // L_flux
   for (int n = tid; n < N; n += 256) {
     const float Kv = Kb[n];
     const float f0 = -Kv * d0b[n] - yqb[n], f1 = -Kv * d1b[n] - yqb[N + n];
-    acc_fl += (double)(mqb[n] * (f0 * f0)) + (double)(mqb[N + n] * (f1 * f1));
+    L[0] += (double)(mqb[n] * (f0 * f0)) + (double)(mqb[N + n] * (f1 * f1));
   }
-  gd_block_sum3(acc_fl, z0, z1, red, tid);
-  const float sf = gd_scale(zeta_flux, acc_fl);
+  block_sum_f64<1>(L, red, tid);
+  const float sf = guidance_scale(zeta_flux, L[0]);
   if (tid == 0) {
     if (sums2) {
       sums3[3 * b] = sums2[2 * b];
       sums3[3 * b + 1] = sums2[2 * b + 1];
     }
-    sums3[3 * b + 2] = (float)acc_fl;
+    sums3[3 * b + 2] = (float)L[0];
   }
   float* wb = w + (size_t)b * 2 * N;
   const float* vi = v_in + (size_t)b * 2 * N + N;
@@ -489,7 +356,19 @@ __global__ void __launch_bounds__(256) psample_update_guided_kernel(const float*
   }
 }
 
+// host side of the two LDS-resident kernels: the B / P check, the dynamic LDS of one launch (8 F floats) and, once per kernel, the
+// opt-in to more than 64 KiB of it
 static const size_t kGuidanceLdsMax = 160 * 1024 - 256;
+static int gd_lds_plan(const char* what, const void* kernel, bool* attr_done, int B, int P, size_t* lds) {
+  if (B <= 0 || P < 5) return fail("%s: need B>0 and P>=5 (got B=%d P=%d)", what, B, P);
+  *lds = (size_t)8 * P * P * sizeof(float);
+  if (*lds > kGuidanceLdsMax) return fail("%s: P=%d does not fit the 160 KiB LDS (one sample per workgroup: P <= 71)", what, P);
+  if (!*attr_done) {
+    (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGuidanceLdsMax);
+    *attr_done = true;
+  }
+  return 0;
+}
 
 }  // namespace pidm
 
@@ -499,17 +378,12 @@ extern "C" int pidm_darcy_guidance_cotangent(const float* x0_pred, const float* 
                                              float inv_h0, float inv_h1, float zeta_obs, float zeta_pde, float* v, float* sums, int B,
                                              int P, void* stream) {
   if (!x0_pred || !obs || !mask || !f_s || !v || !sums) return fail("darcy_guidance_cotangent: null buffer");
-  if (B <= 0 || P < 5) return fail("darcy_guidance_cotangent: need B>0 and P>=5 (got B=%d P=%d)", B, P);
-  const size_t lds = (size_t)8 * P * P * sizeof(float);
-  if (lds > kGuidanceLdsMax) return fail("darcy_guidance_cotangent: P=%d does not fit the 160 KiB LDS (one sample per workgroup: P <= 71)", P);
   static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&guidance_cotangent_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)kGuidanceLdsMax);
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(guidance_cotangent_kernel, dim3((unsigned)B), dim3(256), lds, as_stream(stream), x0_pred, obs, mask, f_s, zeta_obs, zeta_pde, (inv_h1 < 0.f) ? 1.f : -1.f, gd_axis(inv_h0),
-                     gd_axis(inv_h1), v, sums, P);
+  size_t lds;
+  if (int rc = gd_lds_plan("darcy_guidance_cotangent", reinterpret_cast<const void*>(&guidance_cotangent_kernel), &attr_done, B, P, &lds))
+    return rc;
+  hipLaunchKernelGGL(guidance_cotangent_kernel, dim3((unsigned)B), dim3(256), lds, as_stream(stream), x0_pred, obs, mask, f_s, zeta_obs, zeta_pde, (inv_h1 < 0.f) ? 1.f : -1.f, make_axis(inv_h0),
+                     make_axis(inv_h1), v, sums, P);
   PIDM_CHECK_LAUNCH("guidance_cotangent_kernel");
   return 0;
 }
@@ -519,18 +393,13 @@ extern "C" int pidm_darcy_guidance_cotangent_flux(const float* x0_pred, const fl
                                                   float zeta_pde, float zeta_flux, float* v, float* sums, int B, int P, void* stream) {
   if (!x0_pred || !obs || !mask || !flux_obs || !flux_mask || !f_s || !v || !sums)
     return fail("darcy_guidance_cotangent_flux: null buffer");
-  if (B <= 0 || P < 5) return fail("darcy_guidance_cotangent_flux: need B>0 and P>=5 (got B=%d P=%d)", B, P);
-  const size_t lds = (size_t)8 * P * P * sizeof(float);
-  if (lds > kGuidanceLdsMax)
-    return fail("darcy_guidance_cotangent_flux: P=%d does not fit the 160 KiB LDS (one sample per workgroup: P <= 71)", P);
   static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&guidance_cotangent_flux_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)kGuidanceLdsMax);
-    attr_done = true;
-  }
+  size_t lds;
+  if (int rc = gd_lds_plan("darcy_guidance_cotangent_flux", reinterpret_cast<const void*>(&guidance_cotangent_flux_kernel), &attr_done, B,
+                           P, &lds))
+    return rc;
   hipLaunchKernelGGL(guidance_cotangent_flux_kernel, dim3((unsigned)B), dim3(256), lds, as_stream(stream), x0_pred, obs, mask, flux_obs,
-                     flux_mask, f_s, zeta_obs, zeta_pde, zeta_flux, (inv_h1 < 0.f) ? 1.f : -1.f, gd_axis(inv_h0), gd_axis(inv_h1), v,
+                     flux_mask, f_s, zeta_obs, zeta_pde, zeta_flux, (inv_h1 < 0.f) ? 1.f : -1.f, make_axis(inv_h0), make_axis(inv_h1), v,
                      sums, P);
   PIDM_CHECK_LAUNCH("guidance_cotangent_flux_kernel");
   return 0;

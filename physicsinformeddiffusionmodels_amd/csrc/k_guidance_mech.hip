@@ -12,32 +12,11 @@
 // ((3 ndof + E) floats: 117 784 B at nel = 64, one workgroup per CU).  Unlike the training loss the scale factors 1 / sqrt(L) need
 // the sums BEFORE the adjoint: phase 2 leaves the unscaled residual in Z while it sums, one fixed-order block reduction follows,
 // then every thread rescales the entries it wrote itself and fills GU; phases 3 and 4 are mech_kernel<true>'s gather adjoints.
-// The three sums are fp64: a thread adds its entries in index order, then a fixed shuffle tree and four wave sums - no atomics, the
-// same bits run to run and for any batch size (a sample never sees another one).
+// The three sums are fp64: a thread adds its entries in index order, then block_sum_f64 (pidm_common.h, shared with k_guidance.hip)
+// - no atomics, the same bits run to run and for any batch size (a sample never sees another one).
 #include "k_mech_common.h"
 
 namespace pidm {
-
-// fixed-order block sum of three doubles (256 threads = 4 waves); every thread returns with all totals (gd_block_sum3 of
-// k_guidance.hip)
-__device__ __forceinline__ void gm_block_sum3(double& a, double& b, double& c, double (*red)[4], int tid) {
-  for (int off = 32; off > 0; off >>= 1) {
-    a += __shfl_down(a, off);
-    b += __shfl_down(b, off);
-    c += __shfl_down(c, off);
-  }
-  if ((tid & 63) == 0) {
-    red[0][tid >> 6] = a;
-    red[1][tid >> 6] = b;
-    red[2][tid >> 6] = c;
-  }
-  __syncthreads();
-  a = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
-  b = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
-  c = ((red[2][0] + red[2][1]) + red[2][2]) + red[2][3];
-}
-// zeta / sqrt(L), rounded once to fp32; exactly 0 when the term is absent
-__device__ __forceinline__ float gm_scale(float zeta, double L) { return (L > 0.0 && zeta != 0.f) ? (float)((double)zeta / sqrt(L)) : 0.f; }
 
 __global__ void __launch_bounds__(256) mech_guidance_kernel(MechMesh ms, const float* __restrict__ x0,   // [B,3,nel,nel] x0 estimate
                                                             const float* __restrict__ bcs,               // [B,4,nn,nn]
@@ -116,13 +95,14 @@ __global__ void __launch_bounds__(256) mech_guidance_kernel(MechMesh ms, const f
     a_r2 += (double)(res * res);
     sZ[i] = res;
   }
-  gm_block_sum3(a_obs, a_r2, rsum, red, tid);
-  const float shift = (float)(rsum / E) - vf[b];
+  double S[3] = {a_obs, a_r2, rsum};     // L_obs, L_pde, sum of rho
+  block_sum_f64<3>(S, red, tid);
+  const float shift = (float)(S[2] / E) - vf[b];
   const double l_vol = (double)shift * (double)shift;
-  const float so = gm_scale(zeta_obs, a_obs), sr = gm_scale(zeta_pde, a_r2), sv = gm_scale(zeta_vol, l_vol);
+  const float so = guidance_scale(zeta_obs, S[0]), sr = guidance_scale(zeta_pde, S[1]), sv = guidance_scale(zeta_vol, l_vol);
   if (tid == 0) {
-    sums[3 * b] = (float)a_obs;
-    sums[3 * b + 1] = (float)a_r2;
+    sums[3 * b] = (float)S[0];
+    sums[3 * b + 1] = (float)S[1];
     sums[3 * b + 2] = (float)l_vol;
   }
   // every thread rescales the entries of Z it wrote itself: d Phi / d (K U)_i and the direct d Phi / d U_i

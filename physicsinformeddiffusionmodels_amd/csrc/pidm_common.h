@@ -55,6 +55,29 @@ extern long long g_kernel_enqueues;
 // exact n / d for small operands via one mulhi (d == 1 handled by the caller's magic == 0 convention)
 __device__ __forceinline__ int fast_div(int n, int d, unsigned magic) { return d == 1 ? n : (int)__umulhi((unsigned)n, magic); }
 
+// Posterior-guidance kernels (k_guidance.hip, k_guidance_mech.hip): fixed-order block sum of N doubles for 256-thread workgroups
+// (4 waves); every thread returns with all N totals.  Order: the caller's per-thread running sums, the shuffle tree from offset 32
+// down to 1, lane 0 of each wave stores, ONE barrier, ((w0 + w1) + w2) + w3 - no atomics, the same bits run to run and for any
+// batch size.  The barrier also publishes whatever LDS the caller wrote before the call.
+template <int N>
+__device__ __forceinline__ void block_sum_f64(double (&a)[N], double (*red)[4], int tid) {
+  for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+    for (int q = 0; q < N; ++q) a[q] += __shfl_down(a[q], off);
+  }
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int q = 0; q < N; ++q) red[q][tid >> 6] = a[q];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < N; ++q) a[q] = ((red[q][0] + red[q][1]) + red[q][2]) + red[q][3];
+}
+// zeta / sqrt(L) of one guidance term, rounded once to fp32; exactly 0 when the term is absent
+__device__ __forceinline__ float guidance_scale(float zeta, double L) {
+  return (L > 0.0 && zeta != 0.f) ? (float)((double)zeta / sqrt(L)) : 0.f;
+}
+
 // value barrier: the compiler may not look through it (used where a product must be ROUNDED before it is added - no fma).
 // The host emulator's shadow <hip/hip_runtime.h> provides its own definition.
 #ifndef PIDM_OPAQUE_F32

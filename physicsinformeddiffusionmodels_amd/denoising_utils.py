@@ -852,6 +852,12 @@ class DenoisingDiffusion(nn.Module):
         return loss, d, r, q, o
 
     # ---- sampling (src/denoising_utils.py:388-545) ---------------------------------------------------------------
+    def _step_coefs(self, i, surpress_noise):
+        """(c1, c2, sigma) of the ancestral step at time level i: x_{i-1} = c1 x0_hat + c2 x_i + sigma z (host floats)."""
+        ht = self._host_tables
+        sigma = 0.0 if (surpress_noise and i == 0) else float(ht['betas'][i].sqrt())
+        return float(ht['posterior_mean_coef1'][i]), float(ht['posterior_mean_coef2'][i]), sigma
+
     def p_sample(self, x, conditioning_input, t, save_output=False, surpress_noise=False, use_dynamic_threshold=False,
                  residual_func=None, eval_residuals=False, return_optimizer=False, return_inequality=False,
                  residual_correction=False, correction_mode='none'):
@@ -883,12 +889,8 @@ class DenoisingDiffusion(nn.Module):
                 model_out, residual = residual_func.residual_correction(generalized_image_to_b_xy_c(model_out).contiguous())
                 model_out = generalized_b_xy_c_to_image(model_out)
             model_intermediate = model_out.clone() if save_output else None
-            ht = self._host_tables
-            c1, c2 = float(ht['posterior_mean_coef1'][t_int]), float(ht['posterior_mean_coef2'][t_int])
-            sigma = float(ht['betas'][t_int].sqrt())
+            c1, c2, sigma = self._step_coefs(t_int, surpress_noise)
             z = torch.randn_like(x_init)
-            if surpress_noise and t_int == 0:
-                sigma = 0.0
             lib = self.lib
             x0p = model_out.contiguous()
             xi = x_init.contiguous()
@@ -957,6 +959,60 @@ class DenoisingDiffusion(nn.Module):
             return (x_seq, interm_imgs), output[1]
         return x_seq, interm_imgs
 
+    def _obs_like(self, who, name, a, shape, dims, note=""):
+        """Check an observation-like tensor ([B or 1, *shape[1:]]: readings or a 0/1 mask) against `shape`; returns it on the
+        sampler's device as contiguous fp32 [B, ...].  `dims` spells shape[1:] in the error text."""
+        from ._lib import PidmError
+        if not torch.is_tensor(a) or a.dim() != 4 or tuple(a.shape[1:]) != shape[1:] or a.shape[0] not in (1, shape[0]):
+            raise PidmError(f"{who}: {name} must be [B,{dims}] or [1,{dims}] for shape {shape}{note}, got "
+                            f"{tuple(a.shape) if torch.is_tensor(a) else type(a).__name__}")
+        return a.detach().to(device=self.diff_dict['alphas'].device, dtype=torch.float32).expand(shape).contiguous()
+
+    def _guided_loop(self, net, shape, n_sums, guide_below, surpress_noise, keep_history, net_input, cotangent, update, plain,
+                     finish):
+        """The reverse process of the two guided samplers.  Per step: `net_input(x_t)` -> at t < guide_below
+        `input_gradient_pass` -> `cotangent(x0_hat, sums_row) -> (v, est)` -> `pull(v)` -> z -> `update(est, x_t, z, g, c1, c2,
+        sigma, out)`; otherwise `plain(net_in, tt) -> est` -> z -> `pidm_psample_update`.  `est` is what the history keeps as the
+        step's estimate.  z is drawn after the network pass on both branches (one draw per step, after the initial noise).
+        `finish(x_0) -> (x_0, residual)` runs inside the same no-grad / frozen-weights context.  Returns the samplers' result."""
+        from ._engine import frozen_weights, input_gradient_pass
+        dev, lib, B = self.diff_dict['alphas'].device, self.lib, shape[0]
+        guide_below = self.n_steps if guide_below is None else int(guide_below)
+        guidance = torch.zeros(self.n_steps, B, n_sums, dtype=torch.float32, device=dev)
+        cur_x = torch.randn(shape, device=dev)
+        x_seq = [cur_x.detach().cpu()] if keep_history else []
+        interm = [torch.zeros(shape)] if keep_history else []     # (as p_sample_loop(save_output=True): no estimate before the first step)
+        with torch.no_grad(), frozen_weights(net):
+            for k, i in enumerate(reversed(range(self.n_steps))):
+                tt = torch.full((B,), i, device=dev, dtype=torch.long)
+                xi = cur_x.contiguous()
+                c1, c2, sigma = self._step_coefs(i, surpress_noise)
+                out = torch.empty_like(xi)
+                net_in = net_input(xi)
+                if i < guide_below:
+                    x0p, pull = input_gradient_pass(net, net_in, tt)
+                    v, est = cotangent(x0p, guidance[k])
+                    g = pull(v)
+                    z = torch.randn_like(xi)
+                    update(est, xi, z, g, c1, c2, sigma, out)
+                else:
+                    est = plain(net_in, tt)
+                    z = torch.randn_like(xi)
+                    lib.check(lib.pidm_psample_update(ptr(est), ptr(xi), ptr(z), c1, c2, sigma, ptr(out), xi.numel(),
+                                                      stream_ptr(dev)), 'pidm_psample_update')
+                cur_x = out
+                if keep_history:
+                    x_seq.append(cur_x.cpu())
+                    interm.append(est.cpu())
+            last = cur_x
+            cur_x, residual = finish(cur_x)
+            if keep_history and cur_x is not last:      # (replace_observed)
+                x_seq[-1] = cur_x.cpu()
+        if not keep_history:
+            x_seq.append(cur_x)
+            interm.append(est)
+        return (x_seq, interm), {'residual': residual, 'guidance': guidance}
+
     def p_sample_loop_guided(self, shape, residual_func, obs, mask, zeta_obs=1.0, zeta_pde=0.0, guide_below=None,
                              surpress_noise=True, replace_observed=False, keep_history=True, flux_obs=None, flux_mask=None,
                              zeta_flux=0.0):
@@ -982,7 +1038,6 @@ class DenoisingDiffusion(nn.Module):
         the final state, aux['guidance'] [n_steps,B,2] = (L_obs, L_pde) of the x0 estimate per step in the order the steps are
         taken (zeros for unguided steps), kept on the device - nothing is read back inside the loop.  With flux data it is
         [n_steps,B,3] = (L_obs, L_pde, L_flux)."""
-        from ._engine import frozen_weights, input_gradient_pass
         from ._lib import PidmError
         if residual_func is None or getattr(residual_func, 'gov_eqs', None) != 'darcy':
             raise PidmError("p_sample_loop_guided: Darcy only (residual_func must be a ResidualsDarcy)")
@@ -995,62 +1050,33 @@ class DenoisingDiffusion(nn.Module):
         if len(shape) != 4 or shape[1] != 2 or shape[2] != shape[3]:
             raise PidmError(f"p_sample_loop_guided: shape must be (B,2,P,P), got {shape}")
         B, _, P, _ = shape
-        for name, a in (('obs', obs), ('mask', mask)):
-            if not torch.is_tensor(a) or a.dim() != 4 or tuple(a.shape[1:]) != shape[1:] or a.shape[0] not in (1, B):
-                raise PidmError(f"p_sample_loop_guided: {name} must be [B,2,P,P] or [1,2,P,P] for shape {shape}, got "
-                                f"{tuple(a.shape) if torch.is_tensor(a) else type(a).__name__}")
+        who = "p_sample_loop_guided"
         with_flux = flux_obs is not None or flux_mask is not None
-        if with_flux:
-            for name, a in (('flux_obs', flux_obs), ('flux_mask', flux_mask)):
-                if not torch.is_tensor(a) or a.dim() != 4 or tuple(a.shape[1:]) != shape[1:] or a.shape[0] not in (1, B):
-                    raise PidmError(f"p_sample_loop_guided: {name} must be [B,2,P,P] or [1,2,P,P] for shape {shape} (flux_obs and "
-                                    f"flux_mask are given together), got {tuple(a.shape) if torch.is_tensor(a) else type(a).__name__}")
-        dev = self.diff_dict['alphas'].device
-        obs_d = obs.detach().to(device=dev, dtype=torch.float32).expand(shape).contiguous()
-        mask_d = mask.detach().to(device=dev, dtype=torch.float32).expand(shape).contiguous()
-        guide_below = self.n_steps if guide_below is None else int(guide_below)
-        lib, ht = self.lib, self._host_tables
+        obs_d = self._obs_like(who, 'obs', obs, shape, "2,P,P")
+        mask_d = self._obs_like(who, 'mask', mask, shape, "2,P,P")
         flux_kw = {}
         if with_flux:
-            flux_kw = dict(flux_obs=flux_obs.detach().to(device=dev, dtype=torch.float32).expand(shape).contiguous(),
-                           flux_mask=flux_mask.detach().to(device=dev, dtype=torch.float32).expand(shape).contiguous(),
-                           zeta_flux=zeta_flux)
-        guidance = torch.zeros(self.n_steps, B, 3 if with_flux else 2, dtype=torch.float32, device=dev)
-        cur_x = torch.randn(shape, device=dev)
-        x_seq = [cur_x.detach().cpu()] if keep_history else []
-        interm = [torch.zeros(shape)] if keep_history else []     # (as p_sample_loop(save_output=True): no estimate before the first step)
-        with torch.no_grad(), frozen_weights(net):
-            for k, i in enumerate(reversed(range(self.n_steps))):
-                tt = torch.full((B,), i, device=dev, dtype=torch.long)
-                xi = cur_x.contiguous()
-                c1, c2 = float(ht['posterior_mean_coef1'][i]), float(ht['posterior_mean_coef2'][i])
-                sigma = 0.0 if (surpress_noise and i == 0) else float(ht['betas'][i].sqrt())
-                out = torch.empty_like(xi)
-                if i < guide_below:
-                    x0p, pull = input_gradient_pass(net, xi, tt)
-                    v, _ = residual_func.guidance_cotangent(x0p, obs_d, mask_d, zeta_obs, zeta_pde, sums_out=guidance[k], **flux_kw)
-                    g = pull(v)
-                    z = torch.randn_like(xi)
-                    lib.check(lib.pidm_psample_update_guided(ptr(x0p), ptr(xi), ptr(z), ptr(g), c1, c2, sigma, ptr(out), B, 2, P * P,
-                                                             stream_ptr(dev)), 'pidm_psample_update_guided')
-                else:
-                    x0p = net(image_to_b_xy_c(xi), tt).contiguous()
-                    z = torch.randn_like(xi)
-                    lib.check(lib.pidm_psample_update(ptr(x0p), ptr(xi), ptr(z), c1, c2, sigma, ptr(out), xi.numel(),
-                                                      stream_ptr(dev)), 'pidm_psample_update')
-                cur_x = out
-                if keep_history:
-                    x_seq.append(cur_x.cpu())
-                    interm.append(x0p.cpu())
+            together = " (flux_obs and flux_mask are given together)"
+            flux_kw = dict(flux_obs=self._obs_like(who, 'flux_obs', flux_obs, shape, "2,P,P", together),
+                           flux_mask=self._obs_like(who, 'flux_mask', flux_mask, shape, "2,P,P", together), zeta_flux=zeta_flux)
+        lib, dev = self.lib, obs_d.device
+
+        def cotangent(x0p, sums_row):
+            v, _ = residual_func.guidance_cotangent(x0p, obs_d, mask_d, zeta_obs, zeta_pde, sums_out=sums_row, **flux_kw)
+            return v, x0p
+
+        def update(x0p, xi, z, g, c1, c2, sigma, out):
+            lib.check(lib.pidm_psample_update_guided(ptr(x0p), ptr(xi), ptr(z), ptr(g), c1, c2, sigma, ptr(out), B, 2, P * P,
+                                                     stream_ptr(dev)), 'pidm_psample_update_guided')
+
+        def finish(cur_x):
             if replace_observed:
                 cur_x = torch.where(mask_d != 0, obs_d, cur_x)
-                if keep_history:
-                    x_seq[-1] = cur_x.cpu()
-            residual = residual_func.residual_of(cur_x).abs().mean(dim=(1, 2))
-        if not keep_history:
-            x_seq.append(cur_x)
-            interm.append(x0p)
-        return (x_seq, interm), {'residual': residual, 'guidance': guidance}
+            return cur_x, residual_func.residual_of(cur_x).abs().mean(dim=(1, 2))
+
+        return self._guided_loop(net, shape, 3 if with_flux else 2, guide_below, surpress_noise, keep_history,
+                                 net_input=lambda xi: xi, cotangent=cotangent, update=update,
+                                 plain=lambda xi, tt: net(image_to_b_xy_c(xi), tt).contiguous(), finish=finish)
 
     def p_sample_loop_guided_mechanics(self, conditioning_input, shape, residual_func, obs, mask, zeta_obs=1.0, zeta_pde=0.0,
                                        zeta_vol=0.0, guide_below=None, surpress_noise=True, replace_observed=False,
@@ -1079,7 +1105,6 @@ class DenoisingDiffusion(nn.Module):
 
         Not supported: compliance guidance, the `cond=` branch of the network, self-conditioning models, sample estimation
         (`use_ddim_x0`) and meshes beyond the LDS limit of the mechanics kernels."""
-        from ._engine import frozen_weights, input_gradient_pass
         from ._lib import PidmError
         from .residuals_mechanics_K import ResidualsMechanics, _MechResidualFn, resize_image as resize_native
         name = "p_sample_loop_guided_mechanics"
@@ -1102,14 +1127,9 @@ class DenoisingDiffusion(nn.Module):
         for nm, a, want in (('conditioning', conditioning, (B, 3, nn_, nn_)), ('bcs', bcs, (B, 4, nn_, nn_))):
             if not torch.is_tensor(a) or tuple(a.shape) != want:
                 raise PidmError(f"{name}: {nm} must be {list(want)}, got {tuple(a.shape) if torch.is_tensor(a) else type(a).__name__}")
-        for nm, a in (('obs', obs), ('mask', mask)):
-            if not torch.is_tensor(a) or a.dim() != 4 or tuple(a.shape[1:]) != shape[1:] or a.shape[0] not in (1, B):
-                raise PidmError(f"{name}: {nm} must be [B,3,{nn_},{nn_}] or [1,3,{nn_},{nn_}] for shape {shape}, got "
-                                f"{tuple(a.shape) if torch.is_tensor(a) else type(a).__name__}")
-        dev = self.diff_dict['alphas'].device
-        lib, ht = self.lib, self._host_tables
-        obs_d = obs.detach().to(device=dev, dtype=torch.float32).expand(shape).contiguous()
-        mask_d = mask.detach().to(device=dev, dtype=torch.float32).expand(shape).contiguous()
+        obs_d = self._obs_like(name, 'obs', obs, shape, f"3,{nn_},{nn_}")
+        mask_d = self._obs_like(name, 'mask', mask, shape, f"3,{nn_},{nn_}")
+        dev, lib = obs_d.device, self.lib
         cond_d = conditioning.detach().to(device=dev, dtype=torch.float32).contiguous()
         bcs_d = bcs.detach().to(device=dev, dtype=torch.float32).contiguous()
         vf = cond_d[:, 0, 0, 0].contiguous()
@@ -1118,56 +1138,34 @@ class DenoisingDiffusion(nn.Module):
             st.to(dev)
         mesh = (ptr(st.kloc_dev), st.kloc_stride, ptr(st.elem_dofs32), ptr(st.dof_elems32), nel)
         fixed_r = torch.cat((resize_native(cond_d, nel, lib), resize_native(bcs_d, nel, lib)), dim=1)     # resized once: 7 channels
-        guide_below = self.n_steps if guide_below is None else int(guide_below)
-        guidance = torch.zeros(self.n_steps, B, 3, dtype=torch.float32, device=dev)
-        cur_x = torch.randn(shape, device=dev)
-        x_seq = [cur_x.detach().cpu()] if keep_history else []
-        interm = [torch.zeros(shape)] if keep_history else []
-        with torch.no_grad(), frozen_weights(net):
-            for k, i in enumerate(reversed(range(self.n_steps))):
-                tt = torch.full((B,), i, device=dev, dtype=torch.long)
-                xi = cur_x.contiguous()
-                c1, c2 = float(ht['posterior_mean_coef1'][i]), float(ht['posterior_mean_coef2'][i])
-                sigma = 0.0 if (surpress_noise and i == 0) else float(ht['betas'][i].sqrt())
-                out = torch.empty_like(xi)
-                net_in = torch.cat((resize_native(xi, nel, lib), fixed_r), dim=1)                          # 10 channels
-                if i < guide_below:
-                    x0p, pull = input_gradient_pass(net, net_in, tt)
-                    v, mo, _ = residual_func.guidance_cotangent(x0p, bcs_d, vf, obs_d, mask_d, zeta_obs, zeta_pde, zeta_vol,
-                                                                sums_out=guidance[k])
-                    g = pull(v)
-                    z = torch.randn_like(xi)
-                    lib.check(lib.pidm_psample_update_guided_resized(ptr(mo), ptr(xi), ptr(z), ptr(g), c1, c2, sigma, ptr(out), B, 3,
-                                                                     g.shape[-1], nel, nn_, stream_ptr(dev)),
-                              'pidm_psample_update_guided_resized')
-                else:
-                    x0p = net(net_in, tt)
-                    _, mo, _, _ = _MechResidualFn.apply(x0p, bcs_d, vf, st, lib)
-                    z = torch.randn_like(xi)
-                    lib.check(lib.pidm_psample_update(ptr(mo), ptr(xi), ptr(z), c1, c2, sigma, ptr(out), xi.numel(),
-                                                      stream_ptr(dev)), 'pidm_psample_update')
-                cur_x = out
-                if keep_history:
-                    x_seq.append(cur_x.cpu())
-                    interm.append(mo.cpu())
+
+        def cotangent(x0p, sums_row):
+            v, mo, _ = residual_func.guidance_cotangent(x0p, bcs_d, vf, obs_d, mask_d, zeta_obs, zeta_pde, zeta_vol, sums_out=sums_row)
+            return v, mo
+
+        def update(mo, xi, z, g, c1, c2, sigma, out):
+            lib.check(lib.pidm_psample_update_guided_resized(ptr(mo), ptr(xi), ptr(z), ptr(g), c1, c2, sigma, ptr(out), B, 3,
+                                                             g.shape[-1], nel, nn_, stream_ptr(dev)),
+                      'pidm_psample_update_guided_resized')
+
+        def finish(cur_x):
             if replace_observed:
                 on = mask_d != 0
                 on[:, 2, -1, :] = False
                 on[:, 2, :, -1] = False
                 cur_x = torch.where(on, obs_d, cur_x)
-                if keep_history:
-                    x_seq[-1] = cur_x.cpu()
             rho = cur_x[:, 2, :-1, :-1].contiguous()
             u_img = cur_x[:, :2].contiguous()
             res = torch.empty(B, st.neq, dtype=torch.float32, device=dev)
             comp = torch.empty(B, dtype=torch.float32, device=dev)
             lib.check(lib.pidm_mech_apply(ptr(rho), ptr(u_img), ptr(bcs_d), *mesh, ptr(res), ptr(comp), B, stream_ptr(dev)),
                       'pidm_mech_apply')
-            residual = res.abs().mean(dim=1)
-        if not keep_history:
-            x_seq.append(cur_x)
-            interm.append(mo)
-        return (x_seq, interm), {'residual': residual, 'guidance': guidance}
+            return cur_x, res.abs().mean(dim=1)
+
+        return self._guided_loop(net, shape, 3, guide_below, surpress_noise, keep_history,
+                                 net_input=lambda xi: torch.cat((resize_native(xi, nel, lib), fixed_r), dim=1),     # 10 channels
+                                 cotangent=cotangent, update=update,
+                                 plain=lambda net_in, tt: _MechResidualFn.apply(net(net_in, tt), bcs_d, vf, st, lib)[1], finish=finish)
 
     def ddim_sample_x0(self, xt, t, model, shape, reduced_n_steps, ddim_sampling_eta, gov_eqs=None, self_cond=None):
         """Sample estimation (src/denoising_utils.py:712-788).  The reference walks ddim_steps + 2 time levels from t down to 0
