@@ -272,6 +272,23 @@ int pidm_mech_guidance_cotangent(const float* x0_pred, const float* bcs, const f
                                  float zeta_obs, float zeta_pde, float zeta_vol, const float* kloc, int kloc_stride,
                                  const int32_t* elem_dofs, const int32_t* dof_elems, int nel, float* v, float* model_out, float* sums,
                                  int B, void* stream);
+/* The same launch with a compliance term.  C = U . A(rho) U = sum_i U_i (A U)_i with A the closed stiffness ((A U)_i = U_i on a
+ * clamped dof, sum_e rho_e (k_e u_e)_i on a free one): the `compliance` of pidm_mech_residual_fwd, SIGNED, entering Phi linearly
+ * (never clamped, square-rooted or omitted).  comp_form selects what v gains:
+ *   0 'energy'       Phi += zeta_comp C, differentiated through U and rho (the functional of the training loss's lambda_opt term);
+ *   1 'sensitivity'  the adjoint (SIMP) sensitivity of the true compliance f^T K(rho)^-1 f evaluated at the predicted displacement:
+ *                    the gradient of -zeta_comp sg(U) . A(rho) sg(U) (sg = stop-gradient), i.e. the density channel of v gains
+ *                    -zeta_comp sum_{a : dof D_e[a] free} U_{D_e[a]} (k_e u_e)_a and the displacement channels gain nothing.  The
+ *                    sampler steps AGAINST v, so a positive weight adds material where the strain energy is.
+ * sums [B,4] = (L_obs, L_pde, L_vol, C) whatever the weights and the form are.  zeta_comp = 0 gives the v, model_out and first
+ * three sums of pidm_mech_guidance_cotangent.  Same LDS plan, mesh limit, fixed-order fp64 sums and guards; comp_form outside
+ * {0, 1} is refused.  The weights are user parameters; the defaults of the Python layer are placeholders: no trained
+ * checkpoint was available and no sample quality is claimed. */
+int pidm_mech_guidance_cotangent_compliance(const float* x0_pred, const float* bcs, const float* vf, const float* obs,
+                                            const float* mask, float zeta_obs, float zeta_pde, float zeta_vol, float zeta_comp,
+                                            int comp_form, const float* kloc, int kloc_stride, const int32_t* elem_dofs,
+                                            const int32_t* dof_elems, int nel, float* v, float* model_out, float* sums, int B,
+                                            void* stream);
 /* guided ancestral update on a state that the network sees resized: x_prev = c1 x0 + c2 x_t + sigma z - R^T g, everything
  * [B,C,Ho,Ho] except g [B,Hi*Hi,Cg] (the UNet's input-gradient layout, channels 0..C-1 used).  R = pidm_bilinear_resize Ho -> Hi.
  * Gather form, fixed order.  Any Hi, Ho >= 1; 1 <= C <= Cg <= 16; B <= 65535. */

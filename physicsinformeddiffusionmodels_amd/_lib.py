@@ -86,6 +86,7 @@ class PidmLib:
         self._sig("pidm_darcy_guidance_cotangent_flux", [vp, vp, vp, vp, vp, vp, f, f, f, f, f, vp, vp, i, i, vp])
         self._sig("pidm_guidance_flux_general", [vp, vp, vp, vp, vp, f, vp, vp, vp, vp, vp, i, i, vp])
         self._sig("pidm_mech_guidance_cotangent", [vp, vp, vp, vp, vp, f, f, f, vp, i, vp, vp, i, vp, vp, vp, i, vp])
+        self._sig("pidm_mech_guidance_cotangent_compliance", [vp, vp, vp, vp, vp, f, f, f, f, i, vp, i, vp, vp, i, vp, vp, vp, i, vp])
         self._sig("pidm_psample_update_guided_resized", [vp, vp, vp, vp, f, f, f, vp, i, i, i, i, i, vp])
         self._sig("pidm_mech_apply", [vp, vp, vp, vp, i, vp, vp, i, vp, vp, i, vp])
         self._sig("pidm_mech_solve_ws_bytes", [i, i], sz)

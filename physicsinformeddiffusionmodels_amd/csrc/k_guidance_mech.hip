@@ -14,21 +14,36 @@
 // then every thread rescales the entries it wrote itself and fills GU; phases 3 and 4 are mech_kernel<true>'s gather adjoints.
 // The three sums are fp64: a thread adds its entries in index order, then block_sum_f64 (pidm_common.h, shared with k_guidance.hip)
 // - no atomics, the same bits run to run and for any batch size (a sample never sees another one).
+//
+// Compliance term (FORM != kCompNone; pidm_mech_guidance_cotangent_compliance): C = U . K_closed(rho) U = sum_i U_i Kbc_i, the
+// `compliance` of mech_kernel<false> (fp32 products, fp64 sums), is a fourth sum and enters Phi linearly and signed, zeta_comp C.
+//   kCompEnergy       d/d(U, rho) of zeta_comp C - mech_kernel<true>'s g_compliance terms: the cotangent on Kbc_i gains zeta_comp U_i
+//                     (it rides the phase-3 gathers when i is free and is the transposed identity row when i is clamped) and the
+//                     direct gU_i gains zeta_comp Kbc_i;
+//   kCompSensitivity  d/d rho of -zeta_comp sg(U) . K_closed(rho) sg(U), the adjoint sensitivity of f^T K^-1 f at the predicted U:
+//                     v_rho_e gains -zeta_comp sum_{a : D_e[a] free} U_{D_e[a]} (k_e u_e)_a, the displacement channels nothing.
+// Kbc_i waits in GU (idle until the rescale) for the thread that wrote it; the sensitivity form reads the clamp flags of an
+// element's eight dofs from bcs again.  No LDS beyond the plan above, no atomics, no further pass over global memory.
 #include "k_mech_common.h"
 
 namespace pidm {
 
+enum { kCompNone = -1, kCompEnergy = 0, kCompSensitivity = 1 };
+
+template <int FORM>
 __global__ void __launch_bounds__(256) mech_guidance_kernel(MechMesh ms, const float* __restrict__ x0,   // [B,3,nel,nel] x0 estimate
                                                             const float* __restrict__ bcs,               // [B,4,nn,nn]
                                                             const float* __restrict__ vf,                // [B]
                                                             const float* __restrict__ obs,               // [B,3,nn,nn]
                                                             const float* __restrict__ msk,               // [B,3,nn,nn]
-                                                            float zeta_obs, float zeta_pde, float zeta_vol,
+                                                            float zeta_obs, float zeta_pde, float zeta_vol, float zeta_comp,
                                                             float* __restrict__ v,                       // [B,3,nel,nel]
                                                             float* __restrict__ model_out,               // [B,3,nn,nn]
-                                                            float* __restrict__ sums) {                  // [B,3]
+                                                            float* __restrict__ sums) {                  // [B,3] or [B,4]
+  constexpr bool COMP = FORM != kCompNone;
+  constexpr int NS = COMP ? 4 : 3;
   HIP_DYNAMIC_SHARED(float, smem)
-  __shared__ double red[3][4];
+  __shared__ double red[NS][4];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int nel = ms.nel, nn = ms.nn, E = ms.E, ndof = ms.ndof;
   float* sU = smem;
@@ -75,7 +90,7 @@ __global__ void __launch_bounds__(256) mech_guidance_kernel(MechMesh ms, const f
   }
   __syncthreads();
   // ---- phase 2: per dof: (K_closed U)_i and the residual, left UNSCALED in Z; sum r^2 ----
-  double a_r2 = 0.0;
+  double a_r2 = 0.0, a_comp = 0.0;
   for (int i = tid; i < ndof; i += 256) {
     float ku = 0.f;
     for (int s = 0; s < 4; ++s) {
@@ -91,28 +106,41 @@ __global__ void __launch_bounds__(256) mech_guidance_kernel(MechMesh ms, const f
     const int node = i >> 1, d = i & 1;
     const bool masked = bb[(size_t)d * nn * nn + node] != 0.f;
     const float f = masked ? 0.f : bb[(size_t)(2 + d) * nn * nn + node];
-    const float res = (masked ? sU[i] : ku) - f;
+    const float kbc = masked ? sU[i] : ku;
+    const float res = kbc - f;
     a_r2 += (double)(res * res);
     sZ[i] = res;
+    if constexpr (COMP) {
+      a_comp += (double)(sU[i] * kbc);
+      if constexpr (FORM == kCompEnergy) sG[i] = kbc;            // read back below by this thread only
+    }
   }
-  double S[3] = {a_obs, a_r2, rsum};     // L_obs, L_pde, sum of rho
-  block_sum_f64<3>(S, red, tid);
+  double S[NS];                          // L_obs, L_pde, sum of rho (, C)
+  S[0] = a_obs;
+  S[1] = a_r2;
+  S[2] = rsum;
+  if constexpr (COMP) S[3] = a_comp;
+  block_sum_f64<NS>(S, red, tid);
   const float shift = (float)(S[2] / E) - vf[b];
   const double l_vol = (double)shift * (double)shift;
   const float so = guidance_scale(zeta_obs, S[0]), sr = guidance_scale(zeta_pde, S[1]), sv = guidance_scale(zeta_vol, l_vol);
   if (tid == 0) {
-    sums[3 * b] = (float)S[0];
-    sums[3 * b + 1] = (float)S[1];
-    sums[3 * b + 2] = (float)l_vol;
+    sums[NS * b] = (float)S[0];
+    sums[NS * b + 1] = (float)S[1];
+    sums[NS * b + 2] = (float)l_vol;
+    if constexpr (COMP) sums[NS * b + 3] = (float)S[3];
   }
   // every thread rescales the entries of Z it wrote itself: d Phi / d (K U)_i and the direct d Phi / d U_i
   for (int i = tid; i < ndof; i += 256) {
     const int node = i >> 1, d = i & 1;
     const bool masked = bb[(size_t)d * nn * nn + node] != 0.f;
-    const float w = sr * sZ[i];                                  // d Phi / d Kbc_i
+    float w = sr * sZ[i];                                        // d Phi / d Kbc_i
+    if constexpr (FORM == kCompEnergy) w += zeta_comp * sU[i];
     sZ[i] = masked ? 0.f : w;
     const float eo = so * (mb[(size_t)d * nn * nn + node] * (sU[i] - yb[(size_t)d * nn * nn + node]));
-    sG[i] = (masked ? w : 0.f) + eo;
+    float gu = (masked ? w : 0.f) + eo;
+    if constexpr (FORM == kCompEnergy) gu += zeta_comp * sG[i];  // zeta_comp Kbc_i
+    sG[i] = gu;
   }
   __syncthreads();
   // ---- phase 3: gU += K^T z (gather); g_rho_e = z_e^T kloc u_e + volume term + observation term ----
@@ -135,17 +163,24 @@ __global__ void __launch_bounds__(256) mech_guidance_kernel(MechMesh ms, const f
   for (int e = tid; e < E; e += 256) {
     const float* k = ms.kloc + (size_t)e * ms.kloc_stride;
     const int* D = ms.elem_dofs + (size_t)e * 8;
-    float acc = 0.f;
+    float acc = 0.f, se = 0.f;                                   // se = sum over the element's free dofs of U_a (k_e u_e)_a
 #pragma unroll
     for (int a = 0; a < 8; ++a) {
       float t = 0.f;
 #pragma unroll
       for (int q = 0; q < 8; ++q) t = fmaf(k[a * 8 + q], sU[D[q]], t);
       acc = fmaf(sZ[D[a]], t, acc);
+      if constexpr (FORM == kCompSensitivity) {
+        const int i = D[a];
+        const bool masked = bb[(size_t)(i & 1) * nn * nn + (i >> 1)] != 0.f;
+        se = fmaf(masked ? 0.f : sU[i], t, se);
+      }
     }
     const int r = e / nel, c = e - r * nel;
     const size_t on = (size_t)2 * nn * nn + r * nn + c;
-    gx[(size_t)2 * nel * nel + e] = (acc + gs) + so * (mb[on] * (sR[e] - yb[on]));
+    float gr = (acc + gs) + so * (mb[on] * (sR[e] - yb[on]));
+    if constexpr (FORM == kCompSensitivity) gr -= zeta_comp * se;
+    gx[(size_t)2 * nel * nel + e] = gr;
   }
   __syncthreads();
   // ---- phase 4: adjoint of the bilinear up-sampling: each nel x nel pixel gathers the <= 3x3 nodes that read it ----
@@ -234,28 +269,54 @@ __global__ void __launch_bounds__(256) psample_update_guided_resized_kernel(cons
 
 using namespace pidm;
 
+// the guards shared by the two entries (nothing is read or launched when one of them fires), then the launch of one instantiation
+template <int FORM>
+static int mech_guidance_launch(const char* who, const float* x0_pred, const float* bcs, const float* vf, const float* obs,
+                                const float* mask, float zeta_obs, float zeta_pde, float zeta_vol, float zeta_comp, const float* kloc,
+                                int kloc_stride, const int32_t* elem_dofs, const int32_t* dof_elems, int nel, float* v,
+                                float* model_out, float* sums, int B, void* stream) {
+  const int E = nel * nel, nn = nel + 1, ndof = 2 * nn * nn;
+  if (mech_args(nel, E, ndof, kloc, elem_dofs, dof_elems)) return -1;
+  if (!x0_pred || !bcs || !vf || !obs || !mask || !v || !model_out || !sums) return fail("%s: null buffer", who);
+  if (B <= 0) return fail("%s: B must be positive", who);
+  if (nel < 1 || (kloc_stride != 0 && kloc_stride != 64))
+    return fail("%s: need nel >= 1 and kloc_stride 0 or 64 (got nel=%d kloc_stride=%d)", who, nel, kloc_stride);
+  MechMesh ms{elem_dofs, dof_elems, kloc, kloc_stride, E, ndof, nel, nn};
+  const size_t lds = ((size_t)3 * ndof + (size_t)E) * sizeof(float);
+  if (lds > 150 * 1024) return fail("%s: mesh does not fit LDS (nel=%d needs %zu bytes of 153600)", who, nel, lds);
+  static bool attr = false;               // (one per instantiation)
+  if (!attr) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mech_guidance_kernel<FORM>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              150 * 1024);
+    attr = true;
+  }
+  hipLaunchKernelGGL(mech_guidance_kernel<FORM>, dim3((unsigned)B), dim3(256), lds, as_stream(stream), ms, x0_pred, bcs, vf, obs, mask,
+                     zeta_obs, zeta_pde, zeta_vol, zeta_comp, v, model_out, sums);
+  PIDM_CHECK_LAUNCH("mech_guidance_kernel");
+  return 0;
+}
+
 extern "C" int pidm_mech_guidance_cotangent(const float* x0_pred, const float* bcs, const float* vf, const float* obs, const float* mask,
                                             float zeta_obs, float zeta_pde, float zeta_vol, const float* kloc, int kloc_stride,
                                             const int32_t* elem_dofs, const int32_t* dof_elems, int nel, float* v, float* model_out,
                                             float* sums, int B, void* stream) {
-  const int E = nel * nel, nn = nel + 1, ndof = 2 * nn * nn;
-  if (mech_args(nel, E, ndof, kloc, elem_dofs, dof_elems)) return -1;
-  if (!x0_pred || !bcs || !vf || !obs || !mask || !v || !model_out || !sums) return fail("mech_guidance_cotangent: null buffer");
-  if (B <= 0) return fail("mech_guidance_cotangent: B must be positive");
-  if (nel < 1 || (kloc_stride != 0 && kloc_stride != 64))
-    return fail("mech_guidance_cotangent: need nel >= 1 and kloc_stride 0 or 64 (got nel=%d kloc_stride=%d)", nel, kloc_stride);
-  MechMesh ms{elem_dofs, dof_elems, kloc, kloc_stride, E, ndof, nel, nn};
-  const size_t lds = ((size_t)3 * ndof + (size_t)E) * sizeof(float);
-  if (lds > 150 * 1024) return fail("mech_guidance_cotangent: mesh does not fit LDS (nel=%d needs %zu bytes of 153600)", nel, lds);
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mech_guidance_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    attr = true;
-  }
-  hipLaunchKernelGGL(mech_guidance_kernel, dim3((unsigned)B), dim3(256), lds, as_stream(stream), ms, x0_pred, bcs, vf, obs, mask, zeta_obs,
-                     zeta_pde, zeta_vol, v, model_out, sums);
-  PIDM_CHECK_LAUNCH("mech_guidance_kernel");
-  return 0;
+  return mech_guidance_launch<kCompNone>("mech_guidance_cotangent", x0_pred, bcs, vf, obs, mask, zeta_obs, zeta_pde, zeta_vol, 0.f, kloc,
+                                         kloc_stride, elem_dofs, dof_elems, nel, v, model_out, sums, B, stream);
+}
+
+extern "C" int pidm_mech_guidance_cotangent_compliance(const float* x0_pred, const float* bcs, const float* vf, const float* obs,
+                                                       const float* mask, float zeta_obs, float zeta_pde, float zeta_vol,
+                                                       float zeta_comp, int comp_form, const float* kloc, int kloc_stride,
+                                                       const int32_t* elem_dofs, const int32_t* dof_elems, int nel, float* v,
+                                                       float* model_out, float* sums, int B, void* stream) {
+  const char* who = "mech_guidance_cotangent_compliance";
+  if (comp_form == kCompEnergy)
+    return mech_guidance_launch<kCompEnergy>(who, x0_pred, bcs, vf, obs, mask, zeta_obs, zeta_pde, zeta_vol, zeta_comp, kloc, kloc_stride,
+                                             elem_dofs, dof_elems, nel, v, model_out, sums, B, stream);
+  if (comp_form == kCompSensitivity)
+    return mech_guidance_launch<kCompSensitivity>(who, x0_pred, bcs, vf, obs, mask, zeta_obs, zeta_pde, zeta_vol, zeta_comp, kloc,
+                                                  kloc_stride, elem_dofs, dof_elems, nel, v, model_out, sums, B, stream);
+  return fail("%s: comp_form must be 0 (energy) or 1 (sensitivity), got %d", who, comp_form);
 }
 
 extern "C" int pidm_psample_update_guided_resized(const float* x0, const float* x_t, const float* z, const float* g_nhwc, float c1,

@@ -1080,7 +1080,7 @@ class DenoisingDiffusion(nn.Module):
 
     def p_sample_loop_guided_mechanics(self, conditioning_input, shape, residual_func, obs, mask, zeta_obs=1.0, zeta_pde=0.0,
                                        zeta_vol=0.0, guide_below=None, surpress_noise=True, replace_observed=False,
-                                       keep_history=True):
+                                       keep_history=True, zeta_comp=None, compliance_form='energy'):
         """Conditional topology-optimisation sampling by posterior guidance (an extension: the reference has no counterpart).
 
         conditioning_input: `(conditioning [B,3,nn,nn], bcs [B,4,nn,nn])`, or the 3-tuple `p_sample_loop` takes (the solution is
@@ -1096,14 +1096,23 @@ class DenoisingDiffusion(nn.Module):
         `p_sample`.  `replace_observed=True` writes `obs` into the masked entries of the final state (not into the padding of
         channel 2).
 
-        zeta_obs / zeta_pde / zeta_vol are user parameters.  Their defaults are PLACEHOLDERS: no trained checkpoint was available
+        zeta_comp (None: no compliance term) steers by the compliance C = U . A(rho) U of the x0 estimate (A = the closed
+        stiffness; the `optimizer` output of `compute_residual`), signed and entering linearly.  compliance_form='energy':
+        Phi += zeta_comp C, differentiated through the displacement and the density (the functional of the training loss's
+        lambda_opt term).  compliance_form='sensitivity': the step uses the gradient of -zeta_comp sg(U) . A(rho) sg(U) (sg =
+        stop-gradient) instead, the adjoint (SIMP) sensitivity of the true compliance f^T K(rho)^-1 f evaluated at the predicted
+        displacement: only the density is moved, and a positive weight adds material where the strain energy is.  Both are
+        `ResidualsMechanics.guidance_cotangent(..., zeta_comp, compliance_form)`, still one launch.
+
+        zeta_obs / zeta_pde / zeta_vol / zeta_comp are user parameters.  Their defaults are PLACEHOLDERS: no trained checkpoint was available
         when this was written, the right magnitudes depend on the model and the schedule, and nothing here claims sample quality.
 
         Returns `((x_seq, interm), aux)`: aux['residual'] [B] = per-sample mean |r| of the final state (`pidm_mech_apply` with
         rho = x[:,2,:-1,:-1]), aux['guidance'] [n_steps,B,3] = (L_obs, L_pde, L_vol) of the x0 estimate per step in the order the
-        steps are taken (zeros for unguided steps), kept on the device - nothing is read back inside the loop.
+        steps are taken (zeros for unguided steps), kept on the device - nothing is read back inside the loop.  With zeta_comp given
+        (0.0 included) it is [n_steps,B,4] = (L_obs, L_pde, L_vol, C).
 
-        Not supported: compliance guidance, the `cond=` branch of the network, self-conditioning models, sample estimation
+        Not supported: an FE-consistent compliance (a solve per guided step), the `cond=` branch of the network, self-conditioning models, sample estimation
         (`use_ddim_x0`) and meshes beyond the LDS limit of the mechanics kernels."""
         from ._lib import PidmError
         from .residuals_mechanics_K import ResidualsMechanics, _MechResidualFn, resize_image as resize_native
@@ -1112,6 +1121,8 @@ class DenoisingDiffusion(nn.Module):
             raise PidmError(f"{name}: mechanics only (residual_func must be a ResidualsMechanics)")
         if getattr(residual_func, 'use_ddim_x0', False):
             raise PidmError(f"{name}: sample estimation (use_ddim_x0) is not supported")
+        if compliance_form not in residual_func.COMPLIANCE_FORMS:
+            raise PidmError(f"{name}: compliance_form must be 'energy' or 'sensitivity', got {compliance_form!r}")
         net = residual_func.model
         if getattr(net, 'self_condition', False):
             raise PidmError(f"{name}: self-conditioning models are not supported")
@@ -1140,7 +1151,8 @@ class DenoisingDiffusion(nn.Module):
         fixed_r = torch.cat((resize_native(cond_d, nel, lib), resize_native(bcs_d, nel, lib)), dim=1)     # resized once: 7 channels
 
         def cotangent(x0p, sums_row):
-            v, mo, _ = residual_func.guidance_cotangent(x0p, bcs_d, vf, obs_d, mask_d, zeta_obs, zeta_pde, zeta_vol, sums_out=sums_row)
+            v, mo, _ = residual_func.guidance_cotangent(x0p, bcs_d, vf, obs_d, mask_d, zeta_obs, zeta_pde, zeta_vol, sums_out=sums_row,
+                                                        zeta_comp=zeta_comp, compliance_form=compliance_form)
             return v, mo
 
         def update(mo, xi, z, g, c1, c2, sigma, out):
@@ -1162,7 +1174,7 @@ class DenoisingDiffusion(nn.Module):
                       'pidm_mech_apply')
             return cur_x, res.abs().mean(dim=1)
 
-        return self._guided_loop(net, shape, 3, guide_below, surpress_noise, keep_history,
+        return self._guided_loop(net, shape, 3 if zeta_comp is None else 4, guide_below, surpress_noise, keep_history,
                                  net_input=lambda xi: torch.cat((resize_native(xi, nel, lib), fixed_r), dim=1),     # 10 channels
                                  cotangent=cotangent, update=update,
                                  plain=lambda net_in, tt: _MechResidualFn.apply(net(net_in, tt), bcs_d, vf, st, lib)[1], finish=finish)

@@ -269,7 +269,10 @@ class ResidualsMechanics:
                 # cv2.connectedComponents counts the background label too: "!= 2" <=> not exactly one foreground component
                 'fm_error_full_batch': (ncomp != 1).to(torch.int64).cpu()}
 
-    def guidance_cotangent(self, x0_pred, bcs, vf, obs, mask, zeta_obs, zeta_pde, zeta_vol=0.0, sums_out=None):
+    COMPLIANCE_FORMS = {'energy': 0, 'sensitivity': 1}
+
+    def guidance_cotangent(self, x0_pred, bcs, vf, obs, mask, zeta_obs, zeta_pde, zeta_vol=0.0, sums_out=None, zeta_comp=None,
+                           compliance_form='energy'):
         """Posterior-guidance cotangent of an x0 estimate (csrc/k_guidance_mech.hip), one launch.  x0_pred [B,3,nel,nel] (u_x, u_y,
         rho); bcs [B,4,nn,nn]; vf [B]; obs, mask [B,3,nn,nn] (mask 0/1) on the nodal grid nn = nel + 1 of model_out = (u resized,
         rho zero-padded).  Per sample Phi = zeta_obs sqrt(L_obs) + zeta_pde sqrt(L_pde) + zeta_vol sqrt(L_vol) with
@@ -277,7 +280,19 @@ class ResidualsMechanics:
         L_pde = sum r^2 of the residual K(rho) u - f and L_vol = (mean(rho) - vf)^2.  Returns `(v, model_out, sums)`:
         v = dPhi/dx0_pred [B,3,nel,nel], model_out [B,3,nn,nn], sums [B,3] = (L_obs, L_pde, L_vol).  A term whose L is exactly 0
         is omitted.  `sums_out`: a contiguous [B,3] fp32 tensor to write the sums into (no allocation, no copy).  Meshes whose
-        (3 ndof + E) floats do not fit one workgroup's LDS are refused, as by the residual adjoint.  No CPU fallback."""
+        (3 ndof + E) floats do not fit one workgroup's LDS are refused, as by the residual adjoint.  No CPU fallback.
+
+        `zeta_comp` (None: the call above, unchanged) adds the compliance C = U . A(rho) U of the estimate, A the closed stiffness
+        (identity rows on clamped dofs): the `compliance` of `compute_residual(return_optimizer=True)`, signed, entering Phi
+        linearly - never square-rooted or omitted.  Any number, 0.0 included, selects the kernel with the term; sums (and
+        `sums_out`) are then [B,4] = (L_obs, L_pde, L_vol, C).  `compliance_form='energy'`: Phi += zeta_comp C, differentiated
+        through U and rho (the functional of the training loss's lambda_opt term).  `'sensitivity'`: v gains the gradient of
+        -zeta_comp sg(U) . A(rho) sg(U) (sg = stop-gradient), the adjoint (SIMP) sensitivity of the true compliance
+        f^T K(rho)^-1 f evaluated at the predicted displacement: only the density channel changes, and since the sampler steps
+        against v a positive weight adds material where the strain energy is."""
+        if compliance_form not in self.COMPLIANCE_FORMS:
+            raise PidmError(f"guidance_cotangent: compliance_form must be 'energy' or 'sensitivity', got {compliance_form!r}")
+        n_sums = 3 if zeta_comp is None else 4
         nel = self.pixels_per_dim
         nn = nel + 1
         if not torch.is_tensor(x0_pred) or x0_pred.dim() != 4 or tuple(x0_pred.shape[1:]) != (3, nel, nel):
@@ -300,9 +315,15 @@ class ResidualsMechanics:
         bc, vfd, y, m = (a.detach().to(dev).contiguous().float() for a in (bcs, vf, obs, mask))
         v = torch.empty_like(x)
         mo = torch.empty(B, 3, nn, nn, dtype=torch.float32, device=dev)
-        sums = sums_out if sums_out is not None else torch.empty(B, 3, dtype=torch.float32, device=dev)
-        if tuple(sums.shape) != (B, 3) or sums.dtype != torch.float32 or not sums.is_contiguous() or sums.device != dev:
-            raise PidmError('guidance_cotangent: sums_out must be a contiguous fp32 [B,3] tensor on the input device')
+        sums = sums_out if sums_out is not None else torch.empty(B, n_sums, dtype=torch.float32, device=dev)
+        if tuple(sums.shape) != (B, n_sums) or sums.dtype != torch.float32 or not sums.is_contiguous() or sums.device != dev:
+            raise PidmError(f'guidance_cotangent: sums_out must be a contiguous fp32 [B,{n_sums}] tensor on the input device')
+        if zeta_comp is not None:
+            lib.check(lib.pidm_mech_guidance_cotangent_compliance(
+                ptr(x), ptr(bc), ptr(vfd), ptr(y), ptr(m), float(zeta_obs), float(zeta_pde), float(zeta_vol), float(zeta_comp),
+                self.COMPLIANCE_FORMS[compliance_form], ptr(st.kloc_dev), st.kloc_stride, ptr(st.elem_dofs32), ptr(st.dof_elems32),
+                nel, ptr(v), ptr(mo), ptr(sums), B, stream_ptr(dev)), 'pidm_mech_guidance_cotangent_compliance')
+            return v, mo, sums
         lib.check(lib.pidm_mech_guidance_cotangent(ptr(x), ptr(bc), ptr(vfd), ptr(y), ptr(m), float(zeta_obs), float(zeta_pde),
                                                    float(zeta_vol), ptr(st.kloc_dev), st.kloc_stride, ptr(st.elem_dofs32),
                                                    ptr(st.dof_elems32), nel, ptr(v), ptr(mo), ptr(sums), B, stream_ptr(dev)),

@@ -13,7 +13,11 @@ pidm_debug_launch_counts (enqueued launch by launch + inside replayed graphs).  
   (plain) one unguided sampler step: input resize + inference forward + pidm_mech_residual_fwd + pidm_psample_update,
   (b) training-mode forward + full backward with an input gradient,
   (c) one guided step of p_sample_loop_guided_mechanics: input resize + input_gradient_pass + the one-launch cotangent kernel +
-      pull + pidm_psample_update_guided_resized; (c-unet) is its resize + UNet part alone."""
+      pull + pidm_psample_update_guided_resized; (c-unet) is its resize + UNet part alone,
+  (c-comp-e / c-comp-s) the same step with the compliance term (zeta_comp, compliance_form 'energy' / 'sensitivity'): the
+      instantiations of the cotangent kernel with the fourth sum; their yardstick is (c) of the same run,
+  (cot / cot-comp-e / cot-comp-s) the cotangent launch alone, without and with the compliance term; (cot-last) repeats (cot) at
+      the end of the round: what the place in the round is worth for legs this short."""
 import ctypes as C
 import os
 import statistics
@@ -125,10 +129,10 @@ def main_mechanics(out_path, batches):
             for p in m.parameters():
                 p.grad = None
 
-        def leg_c():
+        def leg_c(**comp):
             with torch.no_grad():
                 x0p, pull = input_gradient_pass(m, net_input(), t)
-                v, mo, _ = res.guidance_cotangent(x0p, bcs, vf, obs, mask, 1.0, 1.0, 1.0)
+                v, mo, _ = res.guidance_cotangent(x0p, bcs, vf, obs, mask, 1.0, 1.0, 1.0, **comp)
                 gr = pull(v)
                 L.check(L.pidm_psample_update_guided_resized(ptr(mo), ptr(x), ptr(z), ptr(gr), 0.3, 0.7, 0.05, ptr(out), B, 3, 10, nel,
                                                              nn, stream_ptr(dev)))
@@ -138,11 +142,25 @@ def main_mechanics(out_path, batches):
                 x0p, pull = input_gradient_pass(m, net_input(), t)
                 pull(w)
 
+        x0_fixed = torch.randn(B, 3, nel, nel, generator=g).to(dev)
+        x0_fixed[:, 2] = torch.sigmoid(x0_fixed[:, 2])
+        energy, sens = dict(zeta_comp=1.0, compliance_form='energy'), dict(zeta_comp=1.0, compliance_form='sensitivity')
+
+        def leg_cot(**comp):
+            res.guidance_cotangent(x0_fixed, bcs, vf, obs, mask, 1.0, 1.0, 1.0, **comp)
+
         legs = [("plain  unguided sampler step", leg_plain), ("b  training forward + full backward", leg_b),
-                ("c-unet  resize + input_gradient_pass + pull", leg_c_unet), ("c  guided step", leg_c)]
+                ("c-unet  resize + input_gradient_pass + pull", leg_c_unet), ("c  guided step", leg_c),
+                ("c-comp-e  guided step, compliance (energy)", lambda: leg_c(**energy)),
+                ("c-comp-s  guided step, compliance (sens.)", lambda: leg_c(**sens)),
+                ("cot  cotangent call alone", leg_cot), ("cot-comp-e  cotangent call, energy", lambda: leg_cot(**energy)),
+                ("cot-comp-s  cotangent call, sensitivity", lambda: leg_cot(**sens)),
+                ("cot-last  the cot leg again (leg order)", lambda: leg_cot())]
         times = measure(L, m, legs, lines, B)
-        p_, b_, u_, c_ = (statistics.median(times[k]) for k, _ in legs)
+        p_, b_, u_, c_, ce_, cs_, k_, ke_, ks_, kl_ = (statistics.median(times[k]) for k, _ in legs)
         lines.append(f"  c / plain = {c_ / p_:.3f}   c / b = {c_ / b_:.3f}   c - c-unet = {1e3 * (c_ - u_):+.1f} us (the two guidance kernels)")
+        lines.append(f"  c-comp-e - c = {1e3 * (ce_ - c_):+.1f} us   c-comp-s - c = {1e3 * (cs_ - c_):+.1f} us   "
+                     f"cot-comp-e - cot = {1e3 * (ke_ - k_):+.1f} us   cot-comp-s - cot = {1e3 * (ks_ - k_):+.1f} us   cot-last - cot = {1e3 * (kl_ - k_):+.1f} us")
     finish(lines, out_path)
 
 
