@@ -114,6 +114,10 @@ int pidm_stencil_apply(const float* x, long long x_stride, const pidm_stencil_op
 int pidm_stencil_apply_adjoint(const float* const* gs_host, long long g_stride, const pidm_stencil_op* ops_host, int K,
                                const float* add, long long add_stride, float* gx, long long gx_stride, int N, int H, int W,
                                int periodic, void* stream);
+/* The launch plan both entries above give K operators on N images of H x W, without a launch (host only): out6 = rows and columns
+ * of a tile (TR, TC), tiles along the rows and the columns (ntr, ntc), the halo h and the dynamic LDS bytes of a workgroup.  The
+ * same refusals as the launches (operator count, sizes, reach, image too small). */
+int pidm_stencil_plan(const pidm_stencil_op* ops_host, int K, int N, int H, int W, int periodic, int* out6);
 /* Darcy residual for ANY stencil set      replaces src/residuals_darcy.py:137-183 with fd_acc / bcs as constructor arguments.
  * Same tensors as pidm_darcy_residual_fwd / _bwd; ops4_host = the operators d/d0, d/d1, d2/d0^2, d2/d1^2; bc1_sign = +1 when
  * reverse_d1 (:175-180); the boundary rows keep their meaning under periodic.  A composition that stays on the device: two

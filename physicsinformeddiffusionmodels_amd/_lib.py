@@ -71,6 +71,7 @@ class PidmLib:
         ll, ops = C.c_longlong, C.POINTER(StencilOp)
         self._sig("pidm_stencil_apply", [vp, ll, ops, C.POINTER(vp), i, ll, i, i, i, i, vp])
         self._sig("pidm_stencil_apply_adjoint", [C.POINTER(vp), ll, ops, i, vp, ll, vp, ll, i, i, i, i, vp])
+        self._sig("pidm_stencil_plan", [ops, i, i, i, i, i, C.POINTER(i)])
         self._sig("pidm_darcy_general_ws", [i, i], sz)
         self._sig("pidm_darcy_residual_general_fwd", [vp, vp, ops, i, f, vp, vp, i, i, vp])
         self._sig("pidm_darcy_residual_general_bwd", [vp, vp, ops, i, f, vp, vp, i, i, vp])

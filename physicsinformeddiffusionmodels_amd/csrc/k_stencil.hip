@@ -412,6 +412,16 @@ extern "C" int pidm_stencil_apply_adjoint(const float* const* gs_host, long long
   return launch_stencil_adj(gs_host, g_stride, ops_host, K, add, add_stride, gx, gx_stride, N, H, W, periodic, as_stream(stream));
 }
 
+extern "C" int pidm_stencil_plan(const pidm_stencil_op* ops_host, int K, int N, int H, int W, int periodic, int* out6) {
+  StArgs a;
+  StTile g;
+  size_t lds;
+  if (int rc = st_plan(ops_host, K, N, H, W, periodic, &a, &g, &lds, "stencil_plan")) return rc;
+  if (!out6) return fail("stencil_plan: null buffer");
+  out6[0] = g.TR; out6[1] = g.TC; out6[2] = g.ntr; out6[3] = g.ntc; out6[4] = g.h; out6[5] = (int)lds;
+  return 0;
+}
+
 extern "C" size_t pidm_darcy_general_ws(int B, int P) {
   if (B <= 0 || P <= 0) return 0;
   return (size_t)12 * B * P * P * sizeof(float);
