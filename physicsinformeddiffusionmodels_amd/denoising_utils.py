@@ -10,6 +10,8 @@ configurations compose the same native pieces through autograd with the referenc
 from __future__ import annotations
 
 import contextlib
+import math
+import operator
 import os
 from pathlib import Path  # noqa: F401  (re-exported: main.py uses `Path` from the star-import)
 
@@ -477,6 +479,11 @@ class DenoisingDiffusion(nn.Module):
         self.deferred_scalars = False
         self._scalar_ring, self._scalar_slot = [], 0
         self._early_fetch = None
+        # few-step sampling (extension): what the three sampling loops use when their `sampling_steps` / `eta` keywords are None.
+        # None = the reference's full ancestral walk over all n_steps levels; an int S or a list of levels = strided DDIM steps
+        # (`sampling_timesteps`, `strided_step_coefs`) - an unmodified sample.py is switched by `diffusion.sampling_steps = 50`
+        self.sampling_steps = None
+        self.sampling_eta = 0.0
 
     def _host_scalars(self, scalars, idx_list):
         """floats (or DeferredFloats) for the entries `idx_list` (index tuples) of the device tensor `scalars`"""
@@ -858,9 +865,87 @@ class DenoisingDiffusion(nn.Module):
         sigma = 0.0 if (surpress_noise and i == 0) else float(ht['betas'][i].sqrt())
         return float(ht['posterior_mean_coef1'][i]), float(ht['posterior_mean_coef2'][i]), sigma
 
+    # ---- few-step sampling (extension): strided DDIM steps through the same update kernels -------------------------------
+    @staticmethod
+    def strided_step_coefs(alphas_prod, t, t_prev, eta):
+        """(c1, c2, sigma) of the DDIM step (Song et al.) from level t to level t_prev < t, written on the x0 estimate:
+        x_prev = c1 x0_hat + c2 x_t + sigma z, the form the three update kernels evaluate.  With a = abar_t, p = abar_prev:
+        sigma = eta sqrt((1-p)/(1-a)) sqrt(max(1 - a/p, 0)), c2 = sqrt(max(1 - p - sigma^2, 0)) / sqrt(1-a), c1 = sqrt(p) - c2 sqrt(a)
+        (from x_prev = sqrt(p) x0 + sqrt(1-p-sigma^2) (x_t - sqrt(a) x0)/sqrt(1-a) + sigma z).  eta = 0 is the deterministic
+        sampler, eta = 1 on consecutive levels the ancestral posterior.  t_prev = -1 is the clean sample (p = 1): exactly
+        (1.0, 0.0, 0.0) for every eta.  `alphas_prod`: any 1-D array or tensor of abar; python floats, all arithmetic in float64."""
+        from ._lib import PidmError
+        eta = float(eta)
+        if not eta >= 0.0:
+            raise PidmError(f"strided_step_coefs: eta must be >= 0, got {eta!r}")
+        t, t_prev = int(t), int(t_prev)
+        a = float(alphas_prod[t])
+        p = 1.0 if t_prev < 0 else float(alphas_prod[t_prev])
+        if not (0.0 < a < 1.0 and a <= p <= 1.0):
+            raise PidmError(f"strided_step_coefs: abar must fall from t_prev={t_prev} to t={t} inside (0, 1), got {p!r} -> {a!r}")
+        sigma = eta * math.sqrt((1.0 - p) / (1.0 - a)) * math.sqrt(max(1.0 - a / p, 0.0))
+        c2 = math.sqrt(max(1.0 - p - sigma * sigma, 0.0)) / math.sqrt(1.0 - a)
+        c1 = math.sqrt(p) - c2 * math.sqrt(a)
+        return c1, c2, sigma
+
+    def sampling_timesteps(self, sampling_steps):
+        """The time levels a few-step chain visits, in descending order.  An int S, 2 <= S <= n_steps:
+        linspace(0, n_steps-1, S) rounded (the spacing is at least 1, so no two levels merge; n_steps-1 and 0 are always there;
+        S = n_steps is every level).  A sequence of ints: those levels (unique, inside [0, n_steps-1], at least one), sorted
+        descending.  The last visited level steps to the clean sample.  Anything else raises PidmError."""
+        from ._lib import PidmError
+        T = self.n_steps
+
+        def as_int(v):
+            if isinstance(v, bool):
+                raise TypeError
+            return operator.index(v)
+
+        try:
+            S = as_int(sampling_steps)
+        except TypeError:
+            S = None
+        if S is not None:
+            if not 2 <= S <= T:
+                raise PidmError(f"sampling_steps must be an int in [2, n_steps={T}] or a sequence of time levels, got {sampling_steps!r}")
+            return [int(v) for v in reversed(torch.linspace(0, T - 1, S, dtype=torch.float64).round().tolist())]
+        try:
+            levels = [as_int(v) for v in sampling_steps]
+        except TypeError:
+            raise PidmError(f"sampling_steps must be an int in [2, n_steps={T}] or a sequence of integer time levels, got "
+                            f"{sampling_steps!r}") from None
+        if not levels or len(set(levels)) != len(levels) or min(levels) < 0 or max(levels) > T - 1:
+            raise PidmError(f"sampling_steps: the time levels must be unique, inside [0, {T - 1}] and at least one, got {sampling_steps!r}")
+        return sorted(levels, reverse=True)
+
+    def _strided_plan(self, sampling_steps, eta):
+        """What the sampling loops make of their `sampling_steps` / `eta` keywords (None: the instance attributes): None for the
+        full ancestral walk (eta is then ignored), else (visited levels in descending order, eta)."""
+        from ._lib import PidmError
+        if sampling_steps is None:
+            sampling_steps = getattr(self, 'sampling_steps', None)      # (an object unpickled from before the attributes existed)
+        if sampling_steps is None:
+            return None
+        if eta is None:
+            eta = getattr(self, 'sampling_eta', 0.0)
+        try:
+            eta_f = float(eta)
+        except (TypeError, ValueError):
+            eta_f = float('nan')
+        if not eta_f >= 0.0:
+            raise PidmError(f"eta must be a number >= 0, got {eta!r}")
+        return self.sampling_timesteps(sampling_steps), eta_f
+
+    def _strided_coefs(self, levels, k, eta):
+        """(c1, c2, sigma) of the step from the k-th visited level to the next lower one (the last one: to the clean sample)"""
+        return self.strided_step_coefs(self._host_tables['alphas_prod'], levels[k], levels[k + 1] if k + 1 < len(levels) else -1, eta)
+
     def p_sample(self, x, conditioning_input, t, save_output=False, surpress_noise=False, use_dynamic_threshold=False,
                  residual_func=None, eval_residuals=False, return_optimizer=False, return_inequality=False,
-                 residual_correction=False, correction_mode='none'):
+                 residual_correction=False, correction_mode='none', t_prev=None, eta=0.0):
+        """`t_prev=None`: the reference's ancestral step.  `t_prev` = a lower level, or -1 for the clean sample (extension): the
+        strided DDIM step `strided_step_coefs(abar, t, t_prev, eta)`; the step to -1 is then the chain's last one, which is what
+        `eval_residuals` and the mechanics `sample` flag key on instead of t == 0, and `surpress_noise` has nothing to suppress."""
         assert correction_mode in ['x0', 'xt'] or not residual_correction, 'Correction mode unknown or not given.'
         x_init = x.detach()
         if conditioning_input is not None:
@@ -868,6 +953,7 @@ class DenoisingDiffusion(nn.Module):
             x = torch.cat((x, conditioning), dim=1)
         batch_size = len(x)
         t_int = int(t)
+        is_last = t_int == 0 if t_prev is None else int(t_prev) < 0
         tt = torch.full((batch_size,), t_int, device=x.device, dtype=torch.long)
         model_input = (image_to_b_xy_c(x), tt)
         if residual_func.gov_eqs == 'darcy':
@@ -876,7 +962,7 @@ class DenoisingDiffusion(nn.Module):
         else:
             vf = conditioning[:, 0, 0, 0]
             residual_input = (model_input, bcs, vf, solution)
-            sample = t_int == 0
+            sample = is_last
         # the reference builds (and discards) an autograd graph here (:492-493); nothing downstream needs it
         with torch.no_grad():
             out_dict = residual_func.compute_residual(residual_input, reduce='per-batch', return_model_out=True,
@@ -889,7 +975,10 @@ class DenoisingDiffusion(nn.Module):
                 model_out, residual = residual_func.residual_correction(generalized_image_to_b_xy_c(model_out).contiguous())
                 model_out = generalized_b_xy_c_to_image(model_out)
             model_intermediate = model_out.clone() if save_output else None
-            c1, c2, sigma = self._step_coefs(t_int, surpress_noise)
+            if t_prev is None:
+                c1, c2, sigma = self._step_coefs(t_int, surpress_noise)
+            else:
+                c1, c2, sigma = self.strided_step_coefs(self._host_tables['alphas_prod'], t_int, t_prev, eta)
             z = torch.randn_like(x_init)
             lib = self.lib
             x0p = model_out.contiguous()
@@ -906,7 +995,7 @@ class DenoisingDiffusion(nn.Module):
                 s_thr = torch.quantile(out.reshape(batch_size, -1).abs().float(), 0.9, dim=-1).clamp_(min=1.0)
                 s_thr = right_pad_dims_to(out, s_thr)
                 out = torch.maximum(torch.minimum(out, s_thr), -s_thr) / s_thr
-        if t_int == 0 and eval_residuals:
+        if is_last and eval_residuals:
             aux_out = {'residual': residual}
             if return_optimizer:
                 aux_out['optimized_quant'] = out_dict['optimizer']
@@ -920,9 +1009,20 @@ class DenoisingDiffusion(nn.Module):
 
     def p_sample_loop(self, conditioning_input, shape, save_output=False, surpress_noise=True, use_dynamic_threshold=False,
                       residual_func=None, eval_residuals=False, return_optimizer=False, return_inequality=False,
-                      M_correction=0, N_correction=0, correction_mode='none', keep_history=True):
+                      M_correction=0, N_correction=0, correction_mode='none', keep_history=True, sampling_steps=None, eta=None):
         """`keep_history=False` (extension) skips the two blocking D2H copies per step the reference performs
-        (src/denoising_utils.py:531-532) and returns only the final state in the lists."""
+        (src/denoising_utils.py:531-532) and returns only the final state in the lists.
+
+        `sampling_steps`, `eta` (extension; None: `self.sampling_steps` / `self.sampling_eta`): few-step sampling.  With
+        `sampling_steps` None the full ancestral walk of the reference runs and `eta` is ignored.  An int S or a list of levels
+        (`sampling_timesteps`) visits only those levels: the model is called at each visited t and the same update kernel takes the
+        DDIM coefficients `strided_step_coefs(abar, t, next lower level or -1, eta)`; eta = 0 (default) is deterministic given the
+        initial noise.  One noise tensor is still drawn per visited level, after the network pass, whatever sigma is, so chains
+        that differ in eta consume the generator identically.  The last step's sigma is 0 by construction: `surpress_noise` is
+        accepted and ignored.  `N_correction` counts on the visited levels (t < N_correction), `eval_residuals` reports the last
+        visited level's step, the histories hold one entry per visited level after the initial state, and the aux dict gains
+        'timesteps' (the visited levels)."""
+        plan = self._strided_plan(sampling_steps, eta)
         cur_x = torch.randn(shape, device=self.diff_dict['alphas'].device)
         x_seq = [cur_x.detach().cpu()] if keep_history else []
         interm_imgs = [torch.zeros(shape)] if (save_output and keep_history) else []
@@ -931,7 +1031,10 @@ class DenoisingDiffusion(nn.Module):
         from ._engine import frozen_weights
         net = getattr(residual_func, "model", None)
         with (frozen_weights(net) if isinstance(net, torch.nn.Module) else contextlib.nullcontext()):
-            for i in reversed(range(self.n_steps)):
+            levels = list(reversed(range(self.n_steps))) if plan is None else plan[0]
+            for k, i in enumerate(levels):
+                # (strided: the DDIM step to the next lower visited level, from the last one to the clean sample)
+                step = {} if plan is None else dict(t_prev=levels[k + 1] if k + 1 < len(levels) else -1, eta=plan[1])
                 residual_correction = False
                 if i < N_correction:            # CoCoGen correction inside the last N steps (:520-523)
                     residual_correction = True
@@ -939,7 +1042,7 @@ class DenoisingDiffusion(nn.Module):
                 output = self.p_sample(cur_x.detach(), conditioning_input, i, save_output, surpress_noise, use_dynamic_threshold,
                                        residual_func=residual_func, eval_residuals=eval_residuals,
                                        return_optimizer=return_optimizer, return_inequality=return_inequality,
-                                       residual_correction=residual_correction, correction_mode=correction_mode)
+                                       residual_correction=residual_correction, correction_mode=correction_mode, **step)
                 cur_x, interm_img = output[0]
                 if keep_history:
                     x_seq.append(cur_x.detach().cpu())
@@ -956,6 +1059,8 @@ class DenoisingDiffusion(nn.Module):
             if save_output:
                 interm_imgs.append(interm_img.detach())
         if eval_residuals:
+            if plan is not None:
+                output[1]['timesteps'] = list(levels)
             return (x_seq, interm_imgs), output[1]
         return x_seq, interm_imgs
 
@@ -969,24 +1074,28 @@ class DenoisingDiffusion(nn.Module):
         return a.detach().to(device=self.diff_dict['alphas'].device, dtype=torch.float32).expand(shape).contiguous()
 
     def _guided_loop(self, net, shape, n_sums, guide_below, surpress_noise, keep_history, net_input, cotangent, update, plain,
-                     finish):
+                     finish, plan=None):
         """The reverse process of the two guided samplers.  Per step: `net_input(x_t)` -> at t < guide_below
         `input_gradient_pass` -> `cotangent(x0_hat, sums_row) -> (v, est)` -> `pull(v)` -> z -> `update(est, x_t, z, g, c1, c2,
         sigma, out)`; otherwise `plain(net_in, tt) -> est` -> z -> `pidm_psample_update`.  `est` is what the history keeps as the
         step's estimate.  z is drawn after the network pass on both branches (one draw per step, after the initial noise).
-        `finish(x_0) -> (x_0, residual)` runs inside the same no-grad / frozen-weights context.  Returns the samplers' result."""
+        `finish(x_0) -> (x_0, residual)` runs inside the same no-grad / frozen-weights context.  Returns the samplers' result.
+        `plan` (`_strided_plan`): None walks all n_steps levels with the ancestral coefficients; (levels, eta) visits those levels with
+        the DDIM coefficients of `strided_step_coefs` - same calls, same kernels, one z per visited level; the guidance term is
+        subtracted as it is (not rescaled by the stride)."""
         from ._engine import frozen_weights, input_gradient_pass
         dev, lib, B = self.diff_dict['alphas'].device, self.lib, shape[0]
         guide_below = self.n_steps if guide_below is None else int(guide_below)
-        guidance = torch.zeros(self.n_steps, B, n_sums, dtype=torch.float32, device=dev)
+        levels = list(reversed(range(self.n_steps))) if plan is None else plan[0]
+        guidance = torch.zeros(len(levels), B, n_sums, dtype=torch.float32, device=dev)
         cur_x = torch.randn(shape, device=dev)
         x_seq = [cur_x.detach().cpu()] if keep_history else []
         interm = [torch.zeros(shape)] if keep_history else []     # (as p_sample_loop(save_output=True): no estimate before the first step)
         with torch.no_grad(), frozen_weights(net):
-            for k, i in enumerate(reversed(range(self.n_steps))):
+            for k, i in enumerate(levels):
                 tt = torch.full((B,), i, device=dev, dtype=torch.long)
                 xi = cur_x.contiguous()
-                c1, c2, sigma = self._step_coefs(i, surpress_noise)
+                c1, c2, sigma = self._step_coefs(i, surpress_noise) if plan is None else self._strided_coefs(levels, k, plan[1])
                 out = torch.empty_like(xi)
                 net_in = net_input(xi)
                 if i < guide_below:
@@ -1011,11 +1120,14 @@ class DenoisingDiffusion(nn.Module):
         if not keep_history:
             x_seq.append(cur_x)
             interm.append(est)
-        return (x_seq, interm), {'residual': residual, 'guidance': guidance}
+        aux = {'residual': residual, 'guidance': guidance}
+        if plan is not None:
+            aux['timesteps'] = list(levels)
+        return (x_seq, interm), aux
 
     def p_sample_loop_guided(self, shape, residual_func, obs, mask, zeta_obs=1.0, zeta_pde=0.0, guide_below=None,
                              surpress_noise=True, replace_observed=False, keep_history=True, flux_obs=None, flux_mask=None,
-                             zeta_flux=0.0):
+                             zeta_flux=0.0, sampling_steps=None, eta=None):
         """Conditional Darcy sampling by posterior guidance (an extension: the reference has no counterpart).
 
         obs, mask: [B,2,P,P] or broadcastable [1,2,P,P]; channel 0 is p, channel 1 is K; the mask is 0/1.  K fully observed = the
@@ -1034,6 +1146,12 @@ class DenoisingDiffusion(nn.Module):
         zeta_obs / zeta_pde / zeta_flux are user parameters.  Their defaults are PLACEHOLDERS: no trained checkpoint was available when
         this was written, the right magnitudes depend on the model and the schedule, and nothing here claims sample quality.
 
+        sampling_steps, eta (None: `self.sampling_steps` / `self.sampling_eta`): few-step sampling as in `p_sample_loop` - only the
+        levels of `sampling_timesteps` are visited, with the DDIM coefficients of `strided_step_coefs` in the same update kernels;
+        `guide_below` keeps its meaning on the visited levels and `surpress_noise` is ignored.  The guidance term stays
+        - d Phi / d x_t with the zeta_* as given: it is NOT rescaled by the stride, so a chain of fewer steps is steered by fewer
+        (equally weighted) pushes.  aux['guidance'] then has one row per visited level and aux['timesteps'] lists the levels.
+
         Returns `((x_seq, interm), aux)` like `p_sample_loop(..., eval_residuals=True)`: aux['residual'] [B] = per-sample mean |r| of
         the final state, aux['guidance'] [n_steps,B,2] = (L_obs, L_pde) of the x0 estimate per step in the order the steps are
         taken (zeros for unguided steps), kept on the device - nothing is read back inside the loop.  With flux data it is
@@ -1051,6 +1169,7 @@ class DenoisingDiffusion(nn.Module):
             raise PidmError(f"p_sample_loop_guided: shape must be (B,2,P,P), got {shape}")
         B, _, P, _ = shape
         who = "p_sample_loop_guided"
+        plan = self._strided_plan(sampling_steps, eta)
         with_flux = flux_obs is not None or flux_mask is not None
         obs_d = self._obs_like(who, 'obs', obs, shape, "2,P,P")
         mask_d = self._obs_like(who, 'mask', mask, shape, "2,P,P")
@@ -1076,11 +1195,11 @@ class DenoisingDiffusion(nn.Module):
 
         return self._guided_loop(net, shape, 3 if with_flux else 2, guide_below, surpress_noise, keep_history,
                                  net_input=lambda xi: xi, cotangent=cotangent, update=update,
-                                 plain=lambda xi, tt: net(image_to_b_xy_c(xi), tt).contiguous(), finish=finish)
+                                 plain=lambda xi, tt: net(image_to_b_xy_c(xi), tt).contiguous(), finish=finish, plan=plan)
 
     def p_sample_loop_guided_mechanics(self, conditioning_input, shape, residual_func, obs, mask, zeta_obs=1.0, zeta_pde=0.0,
                                        zeta_vol=0.0, guide_below=None, surpress_noise=True, replace_observed=False,
-                                       keep_history=True, zeta_comp=None, compliance_form='energy'):
+                                       keep_history=True, zeta_comp=None, compliance_form='energy', sampling_steps=None, eta=None):
         """Conditional topology-optimisation sampling by posterior guidance (an extension: the reference has no counterpart).
 
         conditioning_input: `(conditioning [B,3,nn,nn], bcs [B,4,nn,nn])`, or the 3-tuple `p_sample_loop` takes (the solution is
@@ -1107,6 +1226,12 @@ class DenoisingDiffusion(nn.Module):
         zeta_obs / zeta_pde / zeta_vol / zeta_comp are user parameters.  Their defaults are PLACEHOLDERS: no trained checkpoint was available
         when this was written, the right magnitudes depend on the model and the schedule, and nothing here claims sample quality.
 
+        sampling_steps, eta (None: `self.sampling_steps` / `self.sampling_eta`): few-step sampling as in `p_sample_loop` - only the
+        levels of `sampling_timesteps` are visited, with the DDIM coefficients of `strided_step_coefs` in the same update kernel;
+        `guide_below` keeps its meaning on the visited levels and `surpress_noise` is ignored.  The guidance term stays
+        - R^T d Phi / d net_in with the zeta_* as given: it is NOT rescaled by the stride.  aux['guidance'] then has one row per
+        visited level and aux['timesteps'] lists the levels.
+
         Returns `((x_seq, interm), aux)`: aux['residual'] [B] = per-sample mean |r| of the final state (`pidm_mech_apply` with
         rho = x[:,2,:-1,:-1]), aux['guidance'] [n_steps,B,3] = (L_obs, L_pde, L_vol) of the x0 estimate per step in the order the
         steps are taken (zeros for unguided steps), kept on the device - nothing is read back inside the loop.  With zeta_comp given
@@ -1128,6 +1253,7 @@ class DenoisingDiffusion(nn.Module):
             raise PidmError(f"{name}: self-conditioning models are not supported")
         nel = residual_func.pixels_per_dim
         nn_ = nel + 1
+        plan = self._strided_plan(sampling_steps, eta)
         shape = tuple(shape)
         if len(shape) != 4 or shape[1:] != (3, nn_, nn_):
             raise PidmError(f"{name}: shape must be (B,3,{nn_},{nn_}), got {shape}")
@@ -1177,7 +1303,8 @@ class DenoisingDiffusion(nn.Module):
         return self._guided_loop(net, shape, 3 if zeta_comp is None else 4, guide_below, surpress_noise, keep_history,
                                  net_input=lambda xi: torch.cat((resize_native(xi, nel, lib), fixed_r), dim=1),     # 10 channels
                                  cotangent=cotangent, update=update,
-                                 plain=lambda net_in, tt: _MechResidualFn.apply(net(net_in, tt), bcs_d, vf, st, lib)[1], finish=finish)
+                                 plain=lambda net_in, tt: _MechResidualFn.apply(net(net_in, tt), bcs_d, vf, st, lib)[1], finish=finish,
+                                 plan=plan)
 
     def ddim_sample_x0(self, xt, t, model, shape, reduced_n_steps, ddim_sampling_eta, gov_eqs=None, self_cond=None):
         """Sample estimation (src/denoising_utils.py:712-788).  The reference walks ddim_steps + 2 time levels from t down to 0
